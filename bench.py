@@ -1,10 +1,25 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the MI355X render path on BASELINE config C2.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 One step = one full frame of config C2 (README 10-sphere Cornell box,
 1200x900, 1000 spp, 6 bounces; Philox stream, seed 1010) rendered into HBM.
+
+A plain run does only what the headline needs: it sets up, renders W warm-up
+frames, times K frames, writes the last frame with `--dump-outputs` and prints
+the result line (metric, value, unit, ms_per_step, config ...).  Every other
+leg described below (single_process, configs, end_to_end, cpu_baseline, the
+kernel-only timing with its roofline and event counts) takes runs of its own
+and is measured only with `--full`.
+
+`--dump-outputs DIR` writes the planes the last timed step left for its caller
+as DIR/<name>.npy in float64: canva, albedo and normal at N = 1 (the three
+planes rt_render_async fills), the assembled planes on rank 0 at N > 1.  When
+they exceed the 64 MB budget every plane keeps the same pixels, a sample drawn
+once with a fixed seed (dump_outputs).  The scene, camera and Philox seed are
+constants, so the same arguments give the same arrays from run to run.
+
 With N > 1 the bench runs one rank per GPU: either launched by
 torch.distributed.run (RANK/WORLD_SIZE set), or, when `--gpus N` is given
 without that environment, this script starts the N rank processes itself
@@ -25,8 +40,9 @@ library's own one-process multi-device frame (rt_render_gather_async over
 the N devices, its own RCCL ncclGather over xGMI), the path a C caller of
 rt.h uses.
 
-Rank 0 prints ONE JSON line.  Besides the C2 headline it carries (N = 1,
-rank 0): `configs` (C3, C4, C5 and the 10-sphere/100-triangle sweep scene at
+Rank 0 prints ONE JSON line.  With `--full` it carries, besides the C2
+headline (N = 1, rank 0): `configs` (C3, C4, C5 and the 10-sphere/100-triangle
+sweep scene at
 reduced spp, kernel rates and roofline fractions), `end_to_end` (host-buffer
 rates of the drop-ins rt_render_rows and rt_fill_canva x 12 pthreads, i.e.
 upload -> render -> assembled host framebuffer) and `cpu_baseline` with six
@@ -567,13 +583,116 @@ def single_process_leg(scene, p, world, devs, steps, verify_ref=None):
     return rec
 
 
+def kernel_legs(args, ds, p, tiling, local, stream, dev, cam, spheres, world):
+    """--full: the render kernel alone (HIP events on the launch stream, up to 3
+    more frames), its event counts from two 8-spp counting passes and the
+    roofline figures priced from them; the keys this adds to the line."""
+    sptr = stream.cuda_stream
+    # --- kernel-only timing with HIP events on the launch stream ------------
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    n_k = max(1, min(args.steps, 3))
+    ev[0].record(stream)
+    for _ in range(n_k):
+        tipe_rt.render_async(ds, p, tiling, local[0].data_ptr(), local[1].data_ptr(), local[2].data_ptr(),
+                             None, sptr)
+    ev[1].record(stream)
+    torch.cuda.synchronize(dev)
+    kernel_ms = ev[0].elapsed_time(ev[1]) / n_k
+
+    # --- algorithmic FLOPs from a counting pass (8 spp, same frame) ---------
+    p_cnt = tipe_rt.make_params(W, H, 8, BOUNCES, cam, focus=3.0, seed=SEED)
+    d_cnt = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device=dev)
+    tipe_rt.count_async(ds, p_cnt, tiling, d_cnt.data_ptr(), sptr)
+    torch.cuda.synchronize(dev)
+    cnt = [int(x) for x in d_cnt.cpu()]
+    px_local = valid_rows(tiling) * W
+    launch_samples = px_local * SPP
+    flops = flops_per_launch(cnt, len(spheres), 0) * (launch_samples / max(cnt[0], 1))
+    achieved_tflops = flops / (kernel_ms * 1e-3) / 1e12
+    # the reference's own work (no zero-throughput exit: every path runs its
+    # bounces) at the same rate: what the frame costs main.c's algorithm
+    d_ref = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device=dev)
+    with tipe_rt.reference_counts():
+        tipe_rt.count_async(ds, p_cnt, tiling, d_ref.data_ptr(), sptr)
+        torch.cuda.synchronize(dev)
+    cnt_ref = [int(x) for x in d_ref.cpu()]
+    flops_ref = flops_per_launch(cnt_ref, len(spheres), 0) * (launch_samples / max(cnt_ref[0], 1))
+    out_bytes = px_local * 3 * 24
+    traffic, traffic_src = load_pmc_traffic()
+    # HBM bytes by construction (in-run model, beside the committed PMC value):
+    # the render kernel writes one 72-B partial per (chunk, pixel) task,
+    # combine_kernel reads them back once and writes the three output planes
+    # (72 B/px); with one chunk the render kernel writes the frame itself
+    chunks = tipe_rt.types.rt_resolve_spp_chunks(args.chunks, SPP)
+    traffic_model = px_local * 72 * chunks if chunks > 1 else out_bytes
+    traffic_model_frame = 2 * px_local * 72 * chunks + out_bytes if chunks > 1 else out_bytes
+    per = {k: cnt[i] / max(cnt[0], 1) for i, k in enumerate(tipe_rt.COUNTER_NAMES)}
+    return {
+        "roofline": {"bound": "valu", "achieved": round(achieved_tflops, 3), "peak": FP64_VECTOR_PEAK_TFLOPS,
+                     "unit": "TFLOP/s", "frac": round(achieved_tflops / FP64_VECTOR_PEAK_TFLOPS, 4),
+                     "traffic": traffic, "traffic_source": traffic_src,
+                     "traffic_model_bytes_per_launch": traffic_model,
+                     "traffic_model_frame_bytes": traffic_model_frame,
+                     "traffic_model_note": "model: render kernel = chunks x px x 72 B partial writes; frame = "
+                                           "that x 2 (combine_kernel reads them) + 72 B/px output; `traffic` "
+                                           "is the last committed rocprofv3 PMC value (traffic_source)",
+                     "kernel": "render_kernel_q<false, 0, -2, false> (persistent task queue, sphere-only opaque-material instantiation; no sky, no AO, no BVH) + combine_kernel",
+                     "kernel_ms": round(kernel_ms, 3), "flops_per_launch": flops,
+                     "scope": "whole frame (1 GPU)" if world == 1 else
+                              "per rank: rank 0's cyclic row tiles (%d of %d rows), its own kernel time"
+                              % (valid_rows(tiling), H),
+                     "flops_per_sample": round(flops / launch_samples, 1),
+                     "note": "achieved = algorithmic FLOPs of the work done (SURVEY 8d formula on the "
+                             "kernel's own event counts; paths end at zero throughput) / kernel time",
+                     "reference_work": {"flops_per_sample": round(flops_ref / launch_samples, 1),
+                                        "tflops_equivalent": round(flops_ref / (kernel_ms * 1e-3) / 1e12, 3),
+                                        "frac": round(flops_ref / (kernel_ms * 1e-3) / 1e12
+                                                      / FP64_VECTOR_PEAK_TFLOPS, 4)},
+                     "hbm": {"achieved_GBps": round(out_bytes / (kernel_ms * 1e-3) / 1e9, 4),
+                             "peak_GBps": HBM_PEAK_GBS,
+                             "frac": out_bytes / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "algorithmic_bytes_per_launch": out_bytes}},
+        "events_per_sample": {k: round(v, 3) for k, v in per.items()},
+        "kernel_msamples_per_s": round(launch_samples / (kernel_ms * 1e-3) / 1e6, 3),
+    }
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6    # under the 64 MB a dump may take, .npy headers included
+DUMP_SAMPLE_SEED = 20240              # fixed: every run keeps the same pixels
+
+
+def dump_outputs(path, planes):
+    """Write {name: (rows, W, 3) float64 device tensor} as path/<name>.npy.
+    Within the budget the planes are written whole; otherwise each becomes
+    (K, 3): the K pixels (row-major index into rows x W) that a generator
+    seeded with DUMP_SAMPLE_SEED draws without replacement, in ascending
+    order, the same K pixels for every plane."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().cpu().numpy().astype(np.float64, copy=False) for k, v in planes.items()}
+    npx = next(iter(arrs.values())).shape[0] * next(iter(arrs.values())).shape[1]
+    keep = DUMP_BUDGET_BYTES // (len(arrs) * 3 * 8)
+    idx = None
+    if keep < npx:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(npx, size=keep, replace=False))
+    for name, a in arrs.items():
+        assert a.shape[0] * a.shape[1] == npx
+        np.save(os.path.join(path, name + ".npy"), a if idx is None else a.reshape(npx, 3)[idx])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the configs / end_to_end keys")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else the line can carry: kernel-only "
+                         "timing, roofline and event counts, configs, end_to_end, cpu_baseline; at N>1 the "
+                         "single_process leg and the row-tiled configs (default: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the planes of the last timed step as DIR/<name>.npy (float64; a fixed seeded "
+                         "pixel sample when they exceed 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline key")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the configs / end_to_end keys")
     ap.add_argument("--cpu-threads", type=int, default=12)
     ap.add_argument("--chunks", type=int, default=int(os.environ.get("RT_BENCH_CHUNKS", "32")),
                     help="rt_params.spp_chunks (fixed slice grouping of each pixel's samples; the same "
@@ -698,6 +817,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # --- what the last timed step handed its caller ---------------------------
+    if args.dump_outputs and rank == 0:
+        out = locals_[last[0]] if world == 1 else fulls[last[0]]
+        dump_outputs(args.dump_outputs, dict(zip(("canva", "albedo", "normal"), out)))
+
     verified = None
     ref = None
     if args.verify and world > 1 and rank == 0:
@@ -712,7 +836,7 @@ def main():
 
     # --- the library's own single-process multi-device frame (N > 1) --------
     single = None
-    if world > 1 and not args.no_single_process:
+    if args.full and world > 1 and not args.no_single_process:
         # host-side barriers (gloo), so the other ranks wait without a
         # collective kernel spinning on the devices rank 0 now renders on
         cpu_group = dist.new_group(backend="gloo")
@@ -733,7 +857,7 @@ def main():
 
     # --- C3 / C4 / C5 row-tiled over the N ranks ------------------------------
     sharded = None
-    if world > 1 and args.configs:
+    if args.full and world > 1 and args.configs:
         names = [n.strip() for n in args.configs.split(",") if n.strip()]
         bad = [n for n in names if n not in ("C3", "C4", "C5", "nature")]
         if bad:
@@ -741,50 +865,14 @@ def main():
         sharded = configs_sharded(args, rank, world, dev, cam, names)
         torch.cuda.set_device(dev)
 
-    # --- kernel-only timing with HIP events on the launch stream ------------
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    n_k = max(1, min(args.steps, 3))
-    local = locals_[0]
-    ev[0].record(stream)
-    for _ in range(n_k):
-        tipe_rt.render_async(ds, p, tiling, local[0].data_ptr(), local[1].data_ptr(), local[2].data_ptr(),
-                             None, sptr)
-    ev[1].record(stream)
-    torch.cuda.synchronize(dev)
-    kernel_ms = ev[0].elapsed_time(ev[1]) / n_k
-
-    # --- algorithmic FLOPs from a counting pass (8 spp, same frame) ---------
-    p_cnt = tipe_rt.make_params(W, H, 8, BOUNCES, cam, focus=3.0, seed=SEED)
-    d_cnt = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device=dev)
-    tipe_rt.count_async(ds, p_cnt, tiling, d_cnt.data_ptr(), sptr)
-    torch.cuda.synchronize(dev)
-    cnt = [int(x) for x in d_cnt.cpu()]
-    px_local = valid_rows(tiling) * W
-    launch_samples = px_local * SPP
-    flops = flops_per_launch(cnt, len(spheres), 0) * (launch_samples / max(cnt[0], 1))
-    achieved_tflops = flops / (kernel_ms * 1e-3) / 1e12
-    # the reference's own work (no zero-throughput exit: every path runs its
-    # bounces) at the same rate: what the frame costs main.c's algorithm
-    d_ref = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device=dev)
-    with tipe_rt.reference_counts():
-        tipe_rt.count_async(ds, p_cnt, tiling, d_ref.data_ptr(), sptr)
-        torch.cuda.synchronize(dev)
-    cnt_ref = [int(x) for x in d_ref.cpu()]
-    flops_ref = flops_per_launch(cnt_ref, len(spheres), 0) * (launch_samples / max(cnt_ref[0], 1))
-    out_bytes = px_local * 3 * 24
-    traffic, traffic_src = load_pmc_traffic()
-    # HBM bytes by construction (in-run model, beside the committed PMC value):
-    # the render kernel writes one 72-B partial per (chunk, pixel) task,
-    # combine_kernel reads them back once and writes the three output planes
-    # (72 B/px); with one chunk the render kernel writes the frame itself
-    chunks = tipe_rt.types.rt_resolve_spp_chunks(args.chunks, SPP)
-    traffic_model = px_local * 72 * chunks if chunks > 1 else out_bytes
-    traffic_model_frame = 2 * px_local * 72 * chunks + out_bytes if chunks > 1 else out_bytes
+    # --- kernel-only timing, event counts and roofline (runs of their own) --
+    kern = None
+    if args.full:
+        kern = kernel_legs(args, ds, p, tiling, locals_[0], stream, dev, cam, spheres, world)
 
     total_samples = W * H * SPP * args.steps
     value = total_samples / elapsed / 1e6
     if rank == 0:
-        per = {k: cnt[i] / max(cnt[0], 1) for i, k in enumerate(tipe_rt.COUNTER_NAMES)}
         rec = {
             "metric": METRIC, "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
@@ -799,33 +887,9 @@ def main():
                        if world > 1 else None,
                        "rng": "philox4x32-10", "spp_chunks": args.chunks,
                        "arith": "fp64, reference op order (bit-exact vs oracle)"},
-            "roofline": {"bound": "valu", "achieved": round(achieved_tflops, 3), "peak": FP64_VECTOR_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(achieved_tflops / FP64_VECTOR_PEAK_TFLOPS, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "traffic_model_bytes_per_launch": traffic_model,
-                         "traffic_model_frame_bytes": traffic_model_frame,
-                         "traffic_model_note": "model: render kernel = chunks x px x 72 B partial writes; frame = "
-                                               "that x 2 (combine_kernel reads them) + 72 B/px output; `traffic` "
-                                               "is the last committed rocprofv3 PMC value (traffic_source)",
-                         "kernel": "render_kernel_q<false, 0, -2, false> (persistent task queue, sphere-only opaque-material instantiation; no sky, no AO, no BVH) + combine_kernel",
-                         "kernel_ms": round(kernel_ms, 3), "flops_per_launch": flops,
-                         "scope": "whole frame (1 GPU)" if world == 1 else
-                                  "per rank: rank 0's cyclic row tiles (%d of %d rows), its own kernel time"
-                                  % (valid_rows(tiling), H),
-                         "flops_per_sample": round(flops / launch_samples, 1),
-                         "note": "achieved = algorithmic FLOPs of the work done (SURVEY 8d formula on the "
-                                 "kernel's own event counts; paths end at zero throughput) / kernel time",
-                         "reference_work": {"flops_per_sample": round(flops_ref / launch_samples, 1),
-                                            "tflops_equivalent": round(flops_ref / (kernel_ms * 1e-3) / 1e12, 3),
-                                            "frac": round(flops_ref / (kernel_ms * 1e-3) / 1e12
-                                                          / FP64_VECTOR_PEAK_TFLOPS, 4)},
-                         "hbm": {"achieved_GBps": round(out_bytes / (kernel_ms * 1e-3) / 1e9, 4),
-                                 "peak_GBps": HBM_PEAK_GBS,
-                                 "frac": out_bytes / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                 "algorithmic_bytes_per_launch": out_bytes}},
-            "events_per_sample": {k: round(v, 3) for k, v in per.items()},
-            "kernel_msamples_per_s": round(launch_samples / (kernel_ms * 1e-3) / 1e6, 3),
         }
+        if kern is not None:
+            rec.update(kern)
         if verified is not None:
             rec["verified_vs_single_device"] = verified
         if world > 1:
@@ -835,10 +899,10 @@ def main():
             rec["single_process"] = single
         if sharded is not None:
             rec["configs"] = sharded
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             rec["configs"] = configs_extra(dev, stream, cam)
             rec["end_to_end"] = end_to_end(scene, spheres, cam)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(scene, cam, threads=args.cpu_threads)
             rec["speedup_vs_cpu_baseline"] = round(value / rec["cpu_baseline"]["value"], 1)
         print(json.dumps(rec), flush=True)

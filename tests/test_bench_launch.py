@@ -58,8 +58,8 @@ def test_gpus_2_spawns_two_ranks_and_verifies():
     the single-device frame bit for bit -- C4 through the BVH queue kernel
     on cyclic tiles, C5 at 3840x2880."""
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend",
-                        "gloo", "--steps", "1", "--warmup", "0", "--no-extras", "--no-cpu-baseline", "--verify",
-                        "--config-spp", "2"],
+                        "gloo", "--steps", "1", "--warmup", "0", "--full", "--no-extras", "--no-cpu-baseline",
+                        "--verify", "--config-spp", "2"],
                        capture_output=True, text=True, timeout=600, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _json_line(r.stdout)

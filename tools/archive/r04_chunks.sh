@@ -13,7 +13,7 @@ fi
 timeout -k 10 120 tools/probes/split_traffic > $O/split_traffic.json 2>&1 && cat $O/split_traffic.json || exit 1
 for r in 1 2; do
   for c in ${CHUNKS:-32 16 12 8}; do
-    timeout -k 10 200 python bench.py --steps 8 --warmup 2 --no-extras --no-cpu-baseline --chunks $c > $O/bench_c${c}_r$r.json 2>> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+    timeout -k 10 200 python bench.py --steps 8 --warmup 2 --full --no-extras --no-cpu-baseline --chunks $c > $O/bench_c${c}_r$r.json 2>> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/bench_c${c}_r$r.json')); print('bench chunks $c round $r', d['value'], d['roofline']['kernel_ms'])"
   done
 done
