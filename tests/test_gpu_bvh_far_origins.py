@@ -6,7 +6,7 @@ rounding bound of mesh.h:70-94 that grows with |o|).  A ray from farther out
 -- the camera, a hit point on one of the README box's radius-500 walls, on
 main.c:346's radius-1e5 sky sphere -- widens its own slab margins by
 k_delta (|o|_inf - R_b) and its distance slack to s_rel |o|_inf
-(rt_kernels.hip ray32).  Before r06 R_b also covered every sphere, so a sky
+(rt_triangles.h ray32).  Before r06 R_b also covered every sphere, so a sky
 sphere fattened every box, and a camera outside R_b sent the whole launch to
 the every-triangle scan.  Each case is bit for bit against the oracle (whose
 scan has no BVH), with the zero-throughput exit off where rays must leave

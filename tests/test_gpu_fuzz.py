@@ -132,7 +132,7 @@ def test_random_far_scene_bitexact(seed):
     (Hs = (|o| + L) sqrt(a)) and the BVH padding run at |o|, L ~ 1e3-1e5;
     0-24 bounces; spp_chunks 1-3; bit for bit vs the oracle.  Odd seeds run
     with the zero-throughput exit off, so paths go on after a sky hit and
-    BVH walks start at |o| ~ 1e5 (per-ray margins, rt_kernels.hip ray32)."""
+    BVH walks start at |o| ~ 1e5 (per-ray margins, rt_triangles.h ray32)."""
     bundle, p = random_scene(seed, far=True)
     if seed % 2:
         with tipe_rt.reference_counts():
@@ -165,7 +165,7 @@ def test_random_scene_cuda_semantics_bitexact(seed):
 @pytest.mark.parametrize("seed", range(300, 324))
 def test_random_bvh_scene_queue_tiny_grid_bitexact(seed, monkeypatch):
     """Random 100-400 triangle meshes (BVH) with random spheres, through the
-    BVH task-queue kernel (resumable walks, rt_kernels.hip render_kernel_q<..,
+    BVH task-queue kernel (resumable walks, rt_queue.h render_kernel_q<..,
     QB>) on a 1-3 block grid, so every lane runs many tasks and walks span
     rounds across task switches; 5-6 sample slices at 40-48 spp use the
     tapered slice bounds (rt_chunk_bound).  Bit for bit vs the oracle."""

@@ -1,7 +1,7 @@
 """Scenes beyond the candidate pass's 16-bit sphere slot.
 
 The sphere candidate pass tags each running minimum with its sphere slot in
-16 mantissa bits (rt_kernels.hip spheres_closest, RT_CAND_TAG).  Above 65534
+16 mantissa bits (rt_spheres.h spheres_closest, cand_tag).  Above 65534
 spheres the upload switches that pass off (cand_lmax = +inf, ns_cand = 0)
 and every cast takes the exact reference scan (main.c:59-78) -- the
 reference itself has no sphere limit.  Both sides of the threshold must

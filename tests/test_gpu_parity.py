@@ -168,7 +168,7 @@ def test_device_pow_near1_dense(y):
 
 def test_device_normalize_fast_path_is_ieee():
     """normalize() skips the sqrt/division range fixups on in-range lanes and
-    shares 1/|a| (rt_kernels.hip); it must equal a / sqrt(a.a) in IEEE f64
+    shares 1/|a| (rt_vec.h); it must equal a / sqrt(a.a) in IEEE f64
     for every input, including the lanes routed to the generic path."""
     rng = np.random.default_rng(11)
     n = 1 << 18
@@ -510,7 +510,7 @@ def grazing_grid_scene(n=40, seed=11):
     """A fine n x n quad grid (2 n^2 triangles) just above the README box's
     floor, with a small random height on every vertex, seen from a low
     camera: grazing rays cross many boxes, so the cooperative traversal's
-    per-wave LIFO and the lanes' own stacks both fill (rt_kernels.hip
+    per-wave LIFO and the lanes' own stacks both fill (rt_fixed_grid.h
     samples_coop)."""
     from tipe_rt.types import Triangle, Material, Vec3, UV
     rng = np.random.default_rng(seed)

@@ -405,7 +405,7 @@ int make_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling*
     if (!std::isfinite(cam) || !std::isfinite(p->cam.origin.e[0]) || !std::isfinite(p->cam.origin.e[1]) ||
         !std::isfinite(p->cam.origin.e[2]))
         cam = HUGE_VAL;                  // std::max drops NaN: no gate below may pass on a NaN camera
-    // Zero-throughput exit (rt_kernels.hip LanePath::zero_rc): exact when the
+    // Zero-throughput exit (rt_fixed_grid.h LanePath::zero_rc): exact when the
     // shading values are bounded and, with AO, the AO factor stays finite.
     kp.zero_exit = g_zero_exit.load() && p->semantics != RT_SEM_CUDA && sc->mats_bounded &&
                    (!kp.useAO || (AO > 0.0 && AO <= 1000.0 && std::fmax(sc->coord_max, cam) <= 0x1p20));
@@ -415,7 +415,7 @@ int make_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling*
     // hit (det >= 1e-6), so the barycentrics are finite and u = v = +-0
     kp.tex_const = sc->all_tex0 && std::fmax(sc->coord_max, cam) <= 0x1p100;
     // (origins beyond r_scene -- the camera, hit points on far spheres -- widen
-    // the walk's margins per ray, rt_kernels.hip ray32; a non-finite camera
+    // the walk's margins per ray, rt_triangles.h ray32; a non-finite camera
     // takes the every-triangle scan)
     if (sc->bvh && p->accel == RT_ACCEL_AUTO && std::isfinite(cam)) {
         kp.bvh = sc->bvh;
@@ -780,7 +780,7 @@ int rt_scene_upload(int device, const rt_scene* scene, rt_device_scene** out)
 
     // Spheres padded to an even count with never-hit records (r2 = -inf makes
     // the discriminant -inf): the kernel reads them two per s_load_dwordx16.
-    // The candidate pass keeps the winner's slot in 16 mantissa bits (RT_CAND_TAG):
+    // The candidate pass keeps the winner's slot in 16 mantissa bits (cand_tag):
     // above 65534 spheres it is switched off (cand_lmax = +inf, KParams::ns_cand = 0)
     // and every ray takes the exact reference scan -- correct for any count, slower.
     const int ns_pad = (scene->nbSpheres + 1) & ~1;
@@ -791,7 +791,7 @@ int rt_scene_upload(int device, const rt_scene* scene, rt_device_scene** out)
     std::vector<double> sph_disp((size_t)scene->nbSpheres * 3);
     // Candidate-pass bound L >= |C_k| + R_k for every sphere (rounded up, at
     // least 2^-20); a non-finite sphere makes it +inf, which turns the
-    // candidate pass into the exact scan (rt_kernels.hip spheres_closest).
+    // candidate pass into the exact scan (rt_spheres.h spheres_closest).
     long double lmax = 0x1p-20L;
     for (int i = 0; i < scene->nbSpheres; ++i) {
         const rt_sphere& s = scene->sphere_list[i];
@@ -887,7 +887,7 @@ int rt_scene_upload(int device, const rt_scene* scene, rt_device_scene** out)
     // whose hit points cost the padding little (bvh_origin_radius); the padding
     // assumes origins within it, and rays from farther out (the camera, hit
     // points on large spheres such as main.c:346's radius-1e5 sky) widen the
-    // walk's margins by the rest (rt_kernels.hip ray32).  Against r_scene over
+    // walk's margins by the rest (rt_triangles.h ray32).  Against r_scene over
     // every sphere: RTX_MAP/nature under the sky 700 -> 808 Msamples/s at 64 spp
     // (r06, tools/probes/nature_radius.py)
     BvhBuild bvh;
@@ -962,7 +962,7 @@ int rt_scene_upload(int device, const rt_scene* scene, rt_device_scene** out)
     ds->mats_bounded = mats_bounded;
     const auto opaque_mat = [](const DevMat& m) { return !(m.alpha < 0.0001) && !(m.alpha <= 0.99); };
     ds->sph_opaque = std::all_of(sph_mat.begin(), sph_mat.end(), opaque_mat);
-    // tri_material (rt_kernels.hip): the texel's alpha, overridden for
+    // tri_material (rt_shading.h): the texel's alpha, overridden for
     // material indices 1 (1.0), 3 (0.1) and 4 (0.6); the texel index is
     // clamped into the whole table, so every texel counts
     ds->tri_opaque = std::all_of(texels.begin(), texels.end(), opaque_mat);
@@ -971,7 +971,7 @@ int rt_scene_upload(int device, const rt_scene* scene, rt_device_scene** out)
     ds->coord_max = coord_max;
     ds->all_tex0 = scene->nbTriangles > 0 &&
                    std::all_of(tex.begin(), tex.end(), [](const TriTex& x) { return x.tex0 >= 0; });
-    // the affine texel map (rt_kernels.hip tri_texel's fast path), in leaf order
+    // the affine texel map (rt_shading.h tri_texel's fast path), in leaf order
     std::vector<TriUV> tri_uv;
     if (scene->nbTriangles > 0 && !ds->all_tex0) {
         tri_uv.resize(tex.size());

@@ -323,7 +323,7 @@ bool build_bvh(const TriGeo* tri, int nt, double r_scene, BvhBuild& out)
         }
         out.nodes4.swap(bfs);
     }
-    // Traversal stack bound: bvh_step (rt_kernels.hip) pushes every hit
+    // Traversal stack bound: bvh_step (rt_triangles.h) pushes every hit
     // internal child but the one it enters, and every entry on the stack was
     // pushed at an ancestor of the current node, so the stack never holds more
     // than the maximum over root-to-node paths of sum(internal children - 1).
@@ -352,7 +352,7 @@ bool build_bvh(const TriGeo* tri, int nt, double r_scene, BvhBuild& out)
     // delta(R) above is affine in R with slope (e1+e2)^2 4 2^-44 1e6 + 2^-48, the
     // distance slack S_abs = s_rel R: a ray from |o|_inf = R' > r_scene needs the
     // boxes wider by at most k_delta (R' - r_scene) and S_abs = s_rel R' (the walk
-    // adds both per ray, rt_kernels.hip ray32); rounded up
+    // adds both per ray, rt_triangles.h ray32); rounded up
     out.k_delta = bvh_pad_slope(tri, nt, nullptr);
     return std::isfinite(out.k_delta);
 }

@@ -1,5 +1,5 @@
 // rt_bvh.h — triangle BVH layout shared by the host builder (rt_bvh.cpp), the
-// C-ABI (rt_api.cpp) and the kernel (rt_kernels.hip).
+// C-ABI (rt_api.cpp) and the kernel (rt_kernels.hip, rt_triangles.h).
 #pragma once
 #include <vector>
 
@@ -76,7 +76,7 @@ struct BvhBuild {
 
 // Builds over nt precomputed triangles whose coordinates are bounded by
 // r_scene in magnitude; the padding assumes ray origins within r_scene too,
-// and the walk widens it per ray for origins beyond (k_delta, rt_kernels.hip
+// and the walk widens it per ray for origins beyond (k_delta, rt_triangles.h
 // ray32).  false: no BVH (too few triangles or too many nodes) -> brute-force
 // scan.
 bool build_bvh(const TriGeo* tri, int nt, double r_scene, BvhBuild& out);

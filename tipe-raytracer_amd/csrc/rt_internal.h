@@ -1,5 +1,5 @@
 // rt_internal.h — device-side scene layout and launch descriptors shared by
-// the C-ABI (rt_api.cpp) and the kernels (rt_kernels.hip).
+// the C-ABI (rt_api.cpp) and the kernels (rt_kernels.hip and the headers it includes).
 //
 // HBM layout of one uploaded scene (DESIGN.md "Data layout"):
 //   SphCand [ns_pad] 32 B  center, |C|^2 - radius^2 — the candidate pass,
@@ -30,7 +30,7 @@ struct BvhNode4;                                      // rt_bvh.h
 struct BvhNodeH;                                      // rt_bvh.h (64-byte form)
 
 struct SphGeo { double cx, cy, cz, r2; };            // r2 = radius*radius (sphere.h:22)
-// Candidate-pass record (rt_kernels.hip spheres_closest): center and
+// Candidate-pass record (rt_spheres.h spheres_closest): center and
 // k = |C|^2 - r2 (host, long double), so c*a = a*|o|^2 - 2a*o.C + a*k is an
 // FMA chain; padding records have k = +inf (never hit).
 struct SphCand { double cx, cy, cz, k; };
@@ -147,7 +147,7 @@ struct KParams {
                              // (tri_material's alpha overrides); the deep-tree OPQ instantiation
     int ns_cand;             // spheres the candidate pass scans: ns_pad, or 0 when cand_lmax is +inf (every
                              // ray then takes the exact scan: non-finite spheres, or more than 65534
-                             // spheres, whose slots do not fit RT_CAND_TAG's 16 bits)
+                             // spheres, whose slots do not fit cand_tag's 16 bits)
     int stack_cap;           // BVH stack entries of the kernel launch_render picks for this launch
                              // (choose_render; host-set): what COUNT runs check pushes against
     double bvh_rb;           // the origin bound R_b the tree's padding assumed (rt_bvh.h r_scene)

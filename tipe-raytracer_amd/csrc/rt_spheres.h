@@ -1,0 +1,269 @@
+// rt_spheres.h -- hit_sphere (sphere.h:13-47) and the sphere candidate pass (spheres_closest).
+// Part of the single translation unit rt_kernels.hip (included there, in this order).
+#pragma once
+
+namespace rt {
+
+// hit_sphere, sphere.h:13-47, exact reference arithmetic.  two_a = 2*a and
+// four_a = 4*a with a = dot(d, d) (`4*a*c` == (4*a)*c).  A negative
+// numerator decides t < 1e-4 without the division (2a > 0).
+//
+// With fast (two_a in [2^-100, 2^100], rc2a = rcp_refined(two_a)) the
+// divisions run div_core: a hit needs n >= 1e-4*two_a >> 2^-900, and
+// disc <= 2^760 bounds |n| by 2^512, so every quotient that can decide or
+// become t is exact; smaller n give t < 1e-4 on both paths.
+// CU: main_cuda.cu's hit_sphere (sphere.hu:27-45), t1 >= 0 then t2 >= 0.001;
+// its t1 may be tiny, so the fast division also needs |n| >= 2^-900 there.
+template <bool CU>
+__device__ __forceinline__ bool sphere_exact(double cx, double cy, double cz, double r2, const V3 o, const V3 d,
+                                             double two_a, double four_a, bool fast, double rc2a, double& t)
+{
+    const double e1 = CU ? 0.0 : 0.0001, e2 = CU ? 0.001 : 0.0001;
+    const double ocx = o.x - cx, ocy = o.y - cy, ocz = o.z - cz;
+    const double b = 2.0 * (ocx * d.x + ocy * d.y + ocz * d.z);
+    const double c = (ocx * ocx + ocy * ocy + ocz * ocz) - r2;
+    const double disc = b * b - four_a * c;
+    if (!(disc > 0)) return false;
+    const bool f = fast && disc >= 0x1p-760 && disc <= 0x1p760;
+    double sq;
+    if (f) sq = sqrt_core(disc);
+    else sq = sqrt(disc);
+    const double n1 = -b - sq;
+    if (!(n1 < 0.0)) {
+        if (f && (!CU || n1 >= 0x1p-900)) t = div_core(n1, two_a, rc2a);
+        else t = n1 / two_a;
+        if (t >= e1) return true;
+    }
+    const double n2 = -b + sq;
+    if (!(n2 < 0.0)) {
+        if (f && (!CU || n2 >= 0x1p-900)) t = div_core(n2, two_a, rc2a);
+        else t = n2 / two_a;
+        if (t >= e2) return true;
+    }
+    return false;
+}
+
+// The reference's discriminant sign (sphere.h:24-25): COUNT statistics only.
+__device__ __forceinline__ bool disc_positive(const SphGeo& s, const V3 o, const V3 d, double four_a)
+{
+    const double ocx = o.x - s.cx, ocy = o.y - s.cy, ocz = o.z - s.cz;
+    const double b = 2.0 * (ocx * d.x + ocy * d.y + ocz * d.z);
+    const double c = (ocx * ocx + ocy * ocy + ocz * ocz) - s.r2;
+    return b * b - four_a * c > 0;
+}
+
+// Exact reference scan over every sphere (main.c:59-78 with hit_sphere).
+template <bool CU>
+__device__ __forceinline__ int spheres_exact_scan(const KParams& kp, const V3 o, const V3 d, double two_a,
+                                                  double four_a, bool fast, double rc2a, double& t_best)
+{
+    const cdptr sg = (cdptr)kp.sph;
+    double t = dinf();
+    int win = -1;
+    for (int k = 0; k < kp.ns_pad; ++k) {
+        double tk;
+        if (sphere_exact<CU>(sg[4 * k], sg[4 * k + 1], sg[4 * k + 2], sg[4 * k + 3], o, d, two_a, four_a, fast,
+                             rc2a, tk) &&
+            tk < t) {
+            t = tk;
+            win = k;
+        }
+    }
+    t_best = t;
+    return win;
+}
+
+// Closest sphere (main.c:59-78): an FMA candidate pass with rigorous error
+// intervals picks the winner, whose exact reference test then runs alone;
+// any ambiguity reruns the exact scan for that ray (DESIGN.md "Exact closest
+// hit").  Half-b form: h = (o-C).d, D = h^2 - a*c, roots n1,2 = -h -/+ sqrt(D)
+// with t = n/a (the reference's t1,2 = (-b -/+ sqrt(disc))/(2a) scale
+// exactly: b = 2h, disc = 4D).  Intervals are kept in n = a*t units, one
+// per-ray half-width M for every sphere:
+//   h  = od - C.d                       (3 fma; od = o.d per ray)
+//   ca = a|o|^2 - 2a o.C + a*k          (4 fma; k = |C|^2 - r2 from the host)
+//   D  = fma(h, h, -ca)
+// Error bound: with Hs >= (|o| + L) sqrt(a), L >= |C_k| + R_k,
+// |D - D_ref| <= 52.5u*Hs^2 <= 2^-47.3 Hs^2 (u = 2^-53), where D_ref =
+// disc_ref/4.  Rays with D >= T1 = 2^-36 Hs^2 are resolved: the reference's
+// disc > 0, and sa (v_rsq_f64 + one Newton step, <= 2^-45 relative) is within
+// 2^-29.3 Hs of its rounded sqrt, so |n - n_ref| <= 2^-29.29 Hs; a*t_ref lies
+// within u|n| of n_ref.  M = 2^-26 Hs (+ thr*2^-48 for the rounding of
+// thr = a*1e-4) leaves a factor 9.8 of slack.  D < -T2 = -2^-44 Hs^2 is a sure
+// miss; in between (grazing rays) the ray is ambiguous.  Root choice follows
+// hit_sphere: n1 if it may reach 1e-4 (a straddle is ambiguous), else n2.
+// Two winners closer than 2M are ambiguous, so a strictly smaller interval is
+// a strictly smaller t_ref (the reference keeps the first of equal t).
+// Non-finite o, d or Hs^2 > 2^1000 make the ray ambiguous up front.
+// CU (main_cuda.cu's thresholds): t1 >= 0, t2 >= 0.001, one interval pair each.
+// The candidate's n with its low 16 mantissa bits replaced by sphere slot k:
+// one v_and_or_b32 with the mask in a VGPR (msk, loop-invariant; a literal
+// would split it into v_and + v_or) and the wave-uniform slot as its one
+// scalar operand.
+__device__ __forceinline__ double cand_tag(double n, int k, uint32_t msk)
+{
+    uint32_t lo;
+    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(lo) : "v"((uint32_t)__double2loint(n)), "v"(msk), "s"(k));
+    return __hiloint2double(__double2hiint(n), (int)lo);
+}
+
+// min(a, |b|) with an abs source modifier (a >= 0; a NaN b drops out, which
+// only happens for a NaN D: non-finite inputs are already ambiguous)
+__device__ __forceinline__ double dmin_abs2(double a, double b)
+{
+    double r;
+    asm("v_min_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// v_min_f64 / v_max_f64 of two finite, non-NaN operands (the candidate
+// pass's tagged values): fmin/fmax would first canonicalize the bit-built
+// operand (an extra v_max_f64 x, x each).
+__device__ __forceinline__ double dmin_raw(double a, double b)
+{
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ double dmax_raw(double a, double b)
+{
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// main.c:214's `r.x > 0.5 || r.y > 0.5 || r.z > 0.5` as max(x, y, z) > 0.5
+// (a NaN component drops out of v_max_f64 exactly as it fails its own
+// comparison; the throughputs are arithmetic results, never signalling
+// NaNs).  The compiler makes the same fold itself, but through fmax, which
+// canonicalizes all three operands first: 6 VALU instead of 3.
+__device__ __forceinline__ bool any_above_half(V3 r)
+{
+    return dmax_raw(dmax_raw(r.x, r.y), r.z) > 0.5;
+}
+
+template <bool COUNT, bool CU, bool AMGM = false>
+__device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, const V3 d, double a, double two_a,
+                                               double four_a, bool fast, double rc2a, double& t_best, Cnt& cnt)
+{
+    const cdptr sc = (cdptr)kp.sph_cand;
+    const double INF = dinf();
+    const double od = fma(o.z, d.z, fma(o.y, d.y, o.x * d.x));
+    const double aoo = a * fma(o.z, o.z, fma(o.y, o.y, o.x * o.x));
+    const double m2a = -2.0 * a;
+    const double oax = m2a * o.x, oay = m2a * o.y, oaz = m2a * o.z;
+    // Hs >= (|o| + L) sqrt(a): |o|_1 >= |o|_2.  AMGM (the sphere/brute-force
+    // queue kernels without AO or sky): sqrt(a) <= (1 + a)/2, equal at a = 1 (the unit directions
+    // of camera, bounce and AO rays; shorter lerped directions get a looser bound,
+    // more rescans: 1.7e-4 per sample on C2), with 2^-50 for the fma's rounding
+    // for every a >= 0 -- C2 +0.35 %; elsewhere v_rsq_f64 (within 2^-24), which
+    // the BVH instantiations keep (their register allocation lost 1.9 % on C4
+    // with the fma)
+    const double sqa = AMGM ? fma(a, 0.5, 0.5 + 0x1p-50) : (a * __builtin_amdgcn_rsq(a)) * (1.0 + 0x1p-20);
+    const double Hs = ((fabs(o.x) + fabs(o.y)) + fabs(o.z) + kp.cand_lmax) * sqa;
+    const double Hs2 = Hs * Hs;
+    const double T1 = Hs2 * RT_CAND_T1, nT2 = Hs2 * -0x1p-44;
+    const double thr = a * 0.0001;
+    const double thr1 = CU ? 0.0 : thr, thr2 = CU ? a * 0.001 : thr;
+    const double M = fma(thr2, 0x1p-48, Hs * RT_CAND_M);
+    const double thrP = thr1 + M, thrM = thr1 - M, M2 = 2.0 * M;
+    const double thrP2 = thr2 + M, thrM2 = thr2 - M;
+    double bn = INF;
+    int bk;
+    // finite o, d, Hs^2 keep every D below finite; anything else takes the exact scan
+    bool amb = !(fast && Hs2 <= 0x1p1000);
+    uint32_t msk = 0xffff0000u;
+    asm volatile("" : "+v"(msk));
+    // MN (every instantiation but CUDA semantics): the smallest and
+    // second-smallest tagged candidate (bn, bn2; non-candidates enter as a
+    // finite sentinel above 2^1000 that keeps the tag), ambiguity decided once
+    // after the scan (bn2 - bn <= 2M)
+    constexpr bool MN = !CU;
+    double bn2 = __hiloint2double(0x7fefffff, -1);
+    if (MN) bn = bn2;
+    double gmin = bn2;                   // (MN) min |D| over the scan
+    for (int k = 0; k < kp.ns_cand; k += 2) {
+        double g[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) g[j] = sc[4 * k + j];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const double cx = g[4 * e], cy = g[4 * e + 1], cz = g[4 * e + 2], kk = g[4 * e + 3];
+            const double h = fma(-cz, d.z, fma(-cy, d.y, fma(-cx, d.x, od)));
+            const double ca = fma(cz, oaz, fma(cy, oay, fma(cx, oax, fma(a, kk, aoo))));
+            const double D = fma(h, h, -ca);
+            // D finite here.  The ambiguity tests use xor of nested conditions
+            // (a implies b: b && !a == a ^ b) so each comparison is issued once.
+            // MN: one |D| < T1 test (grazing band widened from [-T2, T1) to
+            // (-T1, T1)); D <= -T1 gives a NaN root below, which no comparison
+            // accepts, so `valid` is implied by the candidate test
+            bool valid = true;
+            if (MN) {
+                gmin = dmin_abs2(gmin, D);                  // grazing test once, after the scan
+            } else {
+                valid = D >= T1;
+                amb = amb || (valid != (D >= nT2));         // -T2 <= D < T1: grazing
+            }
+            // sa ~ sqrt(D): v_rsq_f64 + one Newton step (sa = t + t*e/2)
+            const double r0 = __builtin_amdgcn_rsq(D);
+            const double tt = D * r0;
+            const double sa = fma(tt * 0.5, fma(-tt, r0, 1.0), tt);
+            const double n1 = -h - sa;
+            const bool r1 = n1 >= thrM;                     // n1 may reach 1e-4: hit_sphere takes t1
+            // the chosen root: n1 = -h - sa, or n2 = -h + sa; in the sphere-scene queue
+            // kernel (AMGM) as one fma with a selected sign (s * sa is exact; C2
+            // +0.7 %), elsewhere a select (the fma's constants cost the BVH
+            // instantiations registers: sweep -1.4 %)
+            const double n = AMGM ? fma(r1 ? -1.0 : 1.0, sa, -h) : (r1 ? n1 : sa - h);
+            if (MN) {
+                // candidates: every chosen root that may reach 1e-4 (n >= thr - M),
+                // straddling ones included -- they are below any sure root, so
+                // the winner's own test after the scan (bn < thrP) catches them
+                const double nt = cand_tag(n, k + e, msk);
+                const double nc = __hiloint2double(n >= thrM ? __double2hiint(nt) : 0x7fefffff, __double2loint(nt));
+                bn2 = dmin_raw(bn2, dmax_raw(bn, nc));
+                bn = dmin_raw(bn, nc);
+                continue;
+            }
+            const double tP = CU ? (r1 ? thrP : thrP2) : thrP, tM = CU ? (r1 ? thrM : thrM2) : thrM;
+            const bool sure = n >= tP;
+            amb = amb || (valid && (sure != (n >= tM)));    // the chosen root straddles 1e-4
+            const bool cand = valid && sure;
+            // n with its low 16 mantissa bits replaced by the slot (one
+            // v_and_or_b32; host: ns_cand <= 65534); |nt - n| < 2^-36 |n|
+            // <= 2^-34.4 Hs, inside M's slack
+            const double nt = cand_tag(n, k + e, msk);
+            const double diff = nt - bn;
+            const bool closer = cand && diff < -M2;
+            amb = amb || (cand && fabs(diff) <= M2);        // (closer implies |diff| > M2)
+            bn = closer ? nt : bn;
+        }
+    }
+    if (MN) {
+        // the winner is sure (its tagged value, within 2^-36 |n| of n, clears
+        // thr + M with that margin) and every other candidate lies more than
+        // 2M above it; no candidate: bn is the sentinel (> 2^1000)
+        const bool any = bn < 0x1p600;
+        amb = amb || gmin < T1;
+        amb = amb || (any && (bn < thrP * (1.0 + 0x1p-34) || !(bn2 - bn > M2)));
+        bk = any ? (int)((uint32_t)__double2loint(bn) & 0xffffu) : -1;
+    } else {
+        bk = bn < INF ? (int)((uint32_t)__double2loint(bn) & 0xffffu) : -1;
+    }
+    if (COUNT)
+        for (int k = 0; k < kp.ns; ++k) cnt.c[RT_CNT_SPHERE_DISC] += disc_positive(kp.sph[k], o, d, four_a) ? 1 : 0;
+    double t = INF;
+    int win = -1;
+    if (!amb && bk >= 0) {
+        const SphGeo s = kp.sph[bk];
+        if (sphere_exact<CU>(s.cx, s.cy, s.cz, s.r2, o, d, two_a, four_a, fast, rc2a, t)) win = bk;
+        else amb = true;     // cannot happen within the bound; stay exact anyway
+    }
+    if (amb) {               // exact reference scan for this ray
+        if (COUNT) cnt.c[RT_CNT_EXACT_RESCANS] += 1;
+        win = spheres_exact_scan<CU>(kp, o, d, two_a, four_a, fast, rc2a, t);
+    }
+    t_best = t;
+    return win;
+}
+
+}  // namespace rt

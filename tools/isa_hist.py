@@ -7,8 +7,8 @@ source function (where the non-arithmetic VALU issue is).
 Static counts: every instruction of the loop body (basic blocks the compiler
 marks as inside a loop) once, attributed through its .loc inline chain to
   * the phase of render_kernel_q it was inlined into (the kernel's own
-    "// ---- N." section markers, rt_kernels.hip), and
-  * the innermost source function (rt_kernels.hip / rt_device_math.h).
+    "// ---- N." section markers, rt_queue.h), and
+  * the innermost source function (rt_kernels.hip and the csrc headers).
 Costs use the measured gfx950 issue rates (tools/probes/op_rates2/3, SIMD
 cycles per wave64 instruction at 4-8 waves/SIMD), so the "cycles" columns are
 the static issue cost of one pass over each block, not a dynamic profile: a
@@ -23,8 +23,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYM = sys.argv[1] if len(sys.argv) > 1 else "_ZN2rt15render_kernel_qILb0ELi0ELin2ELb0EEEvNS_7KParamsE"
 ASM = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "tipe-raytracer_amd", "rt_kernels_g.s")
-SRC = {"rt_kernels.hip": os.path.join(ROOT, "tipe-raytracer_amd", "csrc", "rt_kernels.hip"),
-       "rt_device_math.h": os.path.join(ROOT, "tipe-raytracer_amd", "csrc", "rt_device_math.h")}
+CSRC = os.path.join(ROOT, "tipe-raytracer_amd", "csrc")
+SRC = {f: os.path.join(CSRC, f) for f in ("rt_kernels.hip", "rt_device_math.h", "rt_vec.h", "rt_spheres.h",
+                                          "rt_triangles.h", "rt_shading.h", "rt_fixed_grid.h", "rt_queue.h")}
+KSRC = "rt_queue.h"          # the file that holds render_kernel_q and its phase markers
 
 # measured issue cost (SIMD cycles per wave64 instruction, 8 waves/SIMD; op_rates2/3)
 COST = {"f64 add/mul/fma": 4.75, "f64 cmp/class": 4.7, "f64 trans": 16.3, "f64 other": 4.8, "f32 fma/mul/add": 2.75,
@@ -95,7 +97,7 @@ def functions(path):
 
 
 FUN = {k: functions(v) for k, v in SRC.items()}
-kern_lines = open(SRC["rt_kernels.hip"]).read().splitlines()
+kern_lines = open(SRC[KSRC]).read().splitlines()
 
 
 def phase_of_line(ln):
@@ -142,7 +144,7 @@ def main():
             base = os.path.basename(f)
             inner = FUN[base].get(int(ln), "?") if base in FUN else base
             for f2, ln2 in chain:
-                if os.path.basename(f2) == "rt_kernels.hip" and kfun_lo <= int(ln2) <= kfun_hi:
+                if os.path.basename(f2) == KSRC and kfun_lo <= int(ln2) <= kfun_hi:
                     phase = phase_of_line(int(ln2))
                     break
         by_phase[phase][cls] += 1

@@ -5,7 +5,7 @@
     RT_HIP_LIB=tools/variants/phase.so python tools/phase_clock.py [c2,c3,c4,sweep] [spp]
 
 The diagnostic build adds s_memtime reads at the round's wave-uniform points
-(rt_kernels.hip RT_PHASE_CLOCK) and writes each wave's cycle sums per phase
+(rt_queue.h, RT_PHASE_CLOCK) and writes each wave's cycle sums per phase
 into its RT_QUEUE_TRACE record.  With four VALU-bound waves per SIMD a
 wave's wall cycles in a phase are in proportion to the issue it takes there,
 so the shares are the round's time shares.  One JSON line per scene."""

@@ -1,6 +1,6 @@
 // Host check of BvhBuild::stack4 (rt_bvh.cpp), the traversal-stack bound the
 // launcher admits trees to the queue kernel's 24-entry LDS stack by.  It runs
-// bvh_step's push rule (rt_kernels.hip: every hit internal child but the one
+// bvh_step's push rule (rt_triangles.h: every hit internal child but the one
 // entered is pushed) as a depth-first walk in which every child box is hit,
 // entering the first or the last internal child, and for random rays against
 // the float boxes; the largest stack size of every walk must stay <= stack4.  Input: triangles as 9 doubles per line on

@@ -17,7 +17,7 @@ __global__ void k(unsigned long long seed, int n, double* maxe0, double* maxe1, 
         double sa = x * r1;
         double e0 = fabs(r0 * sq - 1.0);
         double e1 = fabs(sa - sq) / sq;
-        const double tt = x * r0;                                   // kernel form (rt_kernels.hip)
+        const double tt = x * r0;                                   // kernel form (rt_spheres.h)
         const double sb = fma(tt * 0.5, fma(-tt, r0, 1.0), tt);
         double e2 = fabs(sb - sq) / sq;
         m0 = fmax(m0, e0); m1 = fmax(m1, e1); m2 = fmax(m2, e2);
