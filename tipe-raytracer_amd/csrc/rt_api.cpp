@@ -140,6 +140,9 @@ struct rt_device_scene {
     SphGeo* sph = nullptr;
     SphCand* sph_cand = nullptr;
     double cand_lmax = HUGE_VAL;
+    int* cand_orig = nullptr;        // the sphere index of each candidate record (order_candidates)
+    SphGeo* sph_slot = nullptr;      // sph in candidate-record order
+    int ns_merge = 0;                // leading candidate records that are flagged pairs
     DevMat* sph_mat = nullptr;
     TriGeo* tri = nullptr;
     TriTex* tri_tex = nullptr;
@@ -286,6 +289,8 @@ void free_scene(rt_device_scene* s)
     DeviceGuard g(s->device);
     (void)hipFree(s->sph);
     (void)hipFree(s->sph_cand);
+    (void)hipFree(s->cand_orig);
+    (void)hipFree(s->sph_slot);
     (void)hipFree(s->sph_mat);
     (void)hipFree(s->tri);
     (void)hipFree(s->tri_tex);
@@ -308,6 +313,95 @@ int upload(T** dst, const std::vector<T>& src)
     HIP_TRY(hipMalloc((void**)dst, src.size() * sizeof(T)));
     HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return RT_OK;
+}
+
+// The order of the candidate records and how many leading ones are pairs
+// that may share one root tail (rt_spheres.h spheres_closest; KParams::
+// ns_merge).  The kernel merges a flagged pair's tails in a wave-cast in which
+// no lane's line crosses both spheres, and pays about nine cheap VALU
+// instructions for the test and the selects against a 15-instruction tail, so
+// a pair is worth flagging when that is the common case.
+// Both are a performance hint: the pass gives the same winner for every order
+// and every flag (order[] goes to the device as KParams::cand_orig, which
+// turns the winning record's slot back into the caller's sphere index).
+//
+// The rule: of the lines through the centre of one sphere the fraction
+// 1 - sqrt(1 - (R/d)^2) <= (R/d)^2 crosses a disjoint sphere of radius R whose
+// centre is d away.  Among the kMergeScan spheres of smallest radius (small
+// spheres are the ones few lines cross at all), in ascending radius, each
+// unpaired sphere takes the unpaired partner with the smallest
+// x = (max(R_i, R_j) / d)^2, and the pair is flagged when x <= 1/16 (the
+// README box: its five radius-0.5 spheres give two pairs with x < 0.03; a
+// radius-500 wall overlaps every other sphere and is never flagged).
+// Overlapping, touching and nested spheres have x > 1/16.  An odd count leaves
+// the never-hit padding record, which no line crosses: it is flagged with one
+// more sphere.  The other spheres follow in the caller's order.
+constexpr int kMergeScan = 32;
+int order_candidates(const rt_scene* scene, int ns_pad, std::vector<int>& order)
+{
+    const int ns = scene->nbSpheres;
+    order.clear();
+    std::vector<int> small((size_t)ns);
+    for (int i = 0; i < ns; ++i) small[i] = i;
+    auto rad = [&](int i) { return std::fabs(scene->sphere_list[i].radius); };
+    bool finite = true;
+    for (int i = 0; i < ns; ++i) {
+        const rt_sphere& s = scene->sphere_list[i];
+        finite = finite && std::isfinite(s.radius) && std::isfinite(s.center.e[0]) && std::isfinite(s.center.e[1]) &&
+                 std::isfinite(s.center.e[2]);
+    }
+    std::vector<char> used((size_t)ns, 0);
+    // RT_CAND_MERGE (tests, A/B runs): "off" flags no pair, "all" flags every
+    // pair, both in the caller's order -- the results must not notice
+    const char* mode = std::getenv("RT_CAND_MERGE");
+    const bool all = mode && !std::strcmp(mode, "all"), off = mode && !std::strcmp(mode, "off");
+    if (all || off) {
+        for (int i = 0; i < ns_pad; ++i) order.push_back(i);
+        return all ? ns_pad : 0;
+    }
+    if (finite) {
+        const int m = std::min(ns, kMergeScan);
+        std::partial_sort(small.begin(), small.begin() + m, small.end(),
+                          [&](int x, int y) { return rad(x) != rad(y) ? rad(x) < rad(y) : x < y; });
+        for (int ii = 0; ii < m; ++ii) {
+            const int i = small[ii];
+            if (used[i]) continue;
+            int best = -1;
+            double xbest = HUGE_VAL;
+            for (int jj = ii + 1; jj < m; ++jj) {
+                const int j = small[jj];
+                if (used[j]) continue;
+                const rt_sphere &p = scene->sphere_list[i], &q = scene->sphere_list[j];
+                double d2 = 0.0;
+                for (int a = 0; a < 3; ++a) d2 += (p.center.e[a] - q.center.e[a]) * (p.center.e[a] - q.center.e[a]);
+                const double rm = std::max(rad(i), rad(j));
+                const double x = rm * rm / d2;                  // (d = 0: +inf or NaN, never the smallest)
+                if (x < xbest) {
+                    xbest = x;
+                    best = j;
+                }
+            }
+            if (best >= 0 && xbest <= 1.0 / 16) {
+                used[i] = used[best] = 1;
+                order.push_back(i);
+                order.push_back(best);
+            }
+        }
+        if (ns < ns_pad) {                                      // odd count: one sphere shares the padding's pair
+            for (int ii = 0; ii < m; ++ii)
+                if (!used[small[ii]]) {
+                    used[small[ii]] = 1;
+                    order.push_back(small[ii]);
+                    order.push_back(ns);
+                    break;
+                }
+        }
+    }
+    const int ns_merge = (int)order.size();
+    for (int i = 0; i < ns; ++i)
+        if (!used[i]) order.push_back(i);
+    if ((int)order.size() < ns_pad) order.push_back(ns);        // (the padding record was not placed above)
+    return ns_merge;
 }
 
 int ensure_init_locked()
@@ -347,6 +441,9 @@ int make_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling*
     kp.ns = sc->ns;
     kp.ns_pad = sc->ns_pad;
     kp.ns_cand = std::isfinite(sc->cand_lmax) ? sc->ns_pad : 0;
+    kp.cand_orig = sc->cand_orig;
+    kp.sph_slot = sc->sph_slot;
+    kp.ns_merge = sc->ns_merge;
     kp.nt = sc->nt;
     kp.tw = sc->tw;
     kp.th = sc->th;
@@ -808,6 +905,17 @@ int rt_scene_upload(int device, const rt_scene* scene, rt_device_scene** out)
     }
     const double cand_lmax = std::isfinite((double)lmax) && scene->nbSpheres <= 65534
                                  ? std::nextafter((double)lmax, HUGE_VAL) : HUGE_VAL;
+    // the candidate records in pairing order; SphGeo and the per-sphere tables keep the caller's
+    std::vector<int> cand_orig;
+    const int ns_merge = order_candidates(scene, ns_pad, cand_orig);
+    std::vector<SphGeo> sph_slot((size_t)ns_pad);
+    {
+        const std::vector<SphCand> by_sphere = cand;
+        for (int j = 0; j < ns_pad; ++j) {
+            cand[j] = by_sphere[cand_orig[j]];
+            sph_slot[j] = sph[cand_orig[j]];
+        }
+    }
     std::vector<DevMat> sky;
     if (scene->sky_mat_list)
         for (long long i = 0; i < (long long)scene->sky_width * scene->sky_height; ++i)
@@ -981,6 +1089,7 @@ int rt_scene_upload(int device, const rt_scene* scene, rt_device_scene** out)
     ds->ns = scene->nbSpheres;
     ds->ns_pad = ns_pad;
     ds->cand_lmax = cand_lmax;
+    ds->ns_merge = ns_merge;
     for (int i = 0; i < 6; ++i) ds->cbb[i] = cbb[i];
     ds->nt = scene->nbTriangles;
     ds->tw = scene->nbTriangles > 0 ? scene->tex_width : 1;
@@ -1017,7 +1126,9 @@ int rt_scene_upload(int device, const rt_scene* scene, rt_device_scene** out)
         else
             nodesh.clear();
     }
-    if ((rc = upload(&ds->sph, sph)) || (rc = upload(&ds->sph_cand, cand)) || (rc = upload(&ds->sph_mat, sph_mat)) || (rc = upload(&ds->tri, tri)) ||
+    if ((rc = upload(&ds->sph, sph)) || (rc = upload(&ds->sph_cand, cand)) || (rc = upload(&ds->cand_orig, cand_orig)) ||
+        (rc = upload(&ds->sph_slot, sph_slot)) ||
+(rc = upload(&ds->sph_mat, sph_mat)) || (rc = upload(&ds->tri, tri)) ||
         (rc = upload(&ds->tri_tex, tex)) || (rc = upload(&ds->tri_uv, tri_uv)) || (rc = upload(&ds->texels, texels)) ||
         (rc = upload(&ds->bvh, bvh.nodes4)) || (rc = upload(&ds->bvhh, nodesh)) || (rc = upload(&ds->tri_orig, bvh.order)) ||
         (rc = upload(&ds->sky, sky)) || (rc = upload(&ds->sph_rinv, sph_rinv)) || (rc = upload(&ds->sph_disp, sph_disp)) ||
@@ -1703,6 +1814,9 @@ int rt_verify_sphere_pass(const rt_scene* scene, const double* rays, long long n
     kp.ns = ds->ns;
     kp.ns_pad = ds->ns_pad;
     kp.ns_cand = std::isfinite(ds->cand_lmax) ? ds->ns_pad : 0;
+    kp.cand_orig = ds->cand_orig;
+    kp.sph_slot = ds->sph_slot;
+    kp.ns_merge = ds->ns_merge;
     double* d_rays = nullptr;
     unsigned long long* d = nullptr;
     hipError_t e = hipMalloc((void**)&d_rays, (size_t)n * 6 * sizeof(double));

@@ -5,7 +5,10 @@
 //   SphCand [ns_pad] 32 B  center, |C|^2 - radius^2 — the candidate pass,
 //                          scanned wave-uniformly through the scalar unit,
 //                          two records per s_load_dwordx16; padded to an even
-//                          count with never-hit records (k = +inf)
+//                          count with never-hit records (k = +inf); in the
+//                          host's pairing order (rt_api.cpp order_candidates)
+//   int     [ns_pad]       the sphere index of each candidate record, and
+//   SphGeo  [ns_pad]       its SphGeo (the candidate pass's winner)
 //   SphGeo  [ns_pad] 32 B  center, radius^2 — the exact reference test
 //                          (winner, fallback scan; r2 = -inf padding)
 //   DevMat  [ns]     80 B  sphere material — gathered for the winner only
@@ -154,6 +157,10 @@ struct KParams {
     double bvh_kdelta;       // padding growth per unit of origin beyond it (rt_bvh.h k_delta)
     float bvh_rb_f;          // a float with rb_f (1 + 2^-23) <= R_b (the walk's cheap "inside" test)
     int bvh_far;             // some ray origin may lie beyond R_b: a sphere or the camera does
+    int ns_merge;            // the first ns_merge (even) candidate records are pairs that may share one
+                             // root tail (rt_api.cpp order_candidates; a hint, any value gives the same result)
+    const int* cand_orig;    // [ns_pad] candidate record (slot) j describes sphere cand_orig[j] of sph
+    const SphGeo* sph_slot;  // [ns_pad] sph[cand_orig[j]]: the candidate pass's winner retest
 };
 
 // The render kernel launch_render takes and its BVH walk's LDS stack entries

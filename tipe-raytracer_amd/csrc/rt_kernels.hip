@@ -123,6 +123,9 @@ static_assert(RT_CAND_M * RT_CAND_M * RT_CAND_T1 >= 0x1.8p-89 && RT_CAND_M <= 0x
 #ifndef RT_DIAG_STALE               // tools/probes/stale_visits.py: COUNT walks count visits to nodes whose
 #define RT_DIAG_STALE 0             // entry distance already exceeds the cull distance (in the stack-over
 #endif                              // slot; stack entries below depth 16 only)
+#ifndef RT_DIAG_MERGE               // tools/merge_share.py: render_kernel_q's RT_QUEUE_TRACE record carries the
+#define RT_DIAG_MERGE 0             // wave's flagged sphere pairs that ran one root tail / two (spheres_closest)
+#endif                              // in place of rounds and tasks
 
 // The device code by concern, in definition order (one translation unit).
 #include "rt_vec.h"

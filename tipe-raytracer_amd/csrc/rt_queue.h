@@ -408,6 +408,10 @@ void render_kernel_q(const KParams kp)
     diag_cnt()[0] = 0u;
     diag_cnt()[256] = 0u;
 #endif
+#if RT_DIAG_MERGE
+    diag_merge()[0] = 0u;
+    diag_merge()[4] = 0u;
+#endif
     int x = 0, g = 0, s1 = 0;
     int node = 0, sp = 0, win_orig = 0;      // BVH walk in flight (state SM_TRAV)
     unsigned chunk = 0, p = 0, pixel = 0;
@@ -495,7 +499,7 @@ void render_kernel_q(const KParams kp)
             }
         } else if (QB < 0 && L.state == SM_CAST) {          // sphere-only scenes: no triangle scan
             Cnt cnt;
-            L.win = cast_spheres<false, false, !SKY && AOM != AO_ON>(kp, L.o, L.cast_dir(), L.best, cnt);
+            L.win = cast_spheres<false, false, !SKY && AOM != AO_ON, true>(kp, L.o, L.cast_dir(), L.best, cnt);
             L.kind = L.win >= 0 ? HIT_SPHERE : HIT_NONE;
             L.state = SM_RESOLVE;
         } else if (L.state == SM_CAST) {
@@ -747,6 +751,10 @@ void render_kernel_q(const KParams kp)
 #if RT_DIAG_STALE == 2
         q[2] = diag_cnt()[0];        // diagnostic: node visits and stale visits of the lane
         q[3] = diag_cnt()[256];
+#endif
+#if RT_DIAG_MERGE
+        q[2] = diag_merge()[0];      // diagnostic: the wave's flagged pairs with one tail, with two
+        q[3] = diag_merge()[4];
 #endif
 #if RT_PHASE_CLOCK
         for (int k = 0; k < 5; ++k) q[4 + k] = ph[k];

@@ -130,6 +130,12 @@ __device__ __forceinline__ double dmax_raw(double a, double b)
     asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+// a = min(a, b) in a's own register: a loop-carried minimum that is updated on
+// two sides of a branch otherwise ends in a v_mov_b64 per side at the latch
+__device__ __forceinline__ void dmin_acc(double& a, double b)
+{
+    asm("v_min_f64 %0, %0, %1" : "+v"(a) : "v"(b));
+}
 
 // main.c:214's `r.x > 0.5 || r.y > 0.5 || r.z > 0.5` as max(x, y, z) > 0.5
 // (a NaN component drops out of v_max_f64 exactly as it fails its own
@@ -141,7 +147,47 @@ __device__ __forceinline__ bool any_above_half(V3 r)
     return dmax_raw(dmax_raw(r.x, r.y), r.z) > 0.5;
 }
 
-template <bool COUNT, bool CU, bool AMGM = false>
+#if RT_DIAG_MERGE
+// tools/merge_share.py: flagged pairs that took one tail [0] / two tails [4],
+// per wave of the block (every active lane adds the same wave-uniform step)
+__device__ __forceinline__ unsigned* diag_merge()
+{
+    __shared__ unsigned dm_lds[8];
+    return dm_lds + (threadIdx.x >> 6);
+}
+#endif
+
+// (MN) The root tail of one sphere of the candidate scan: its tagged
+// candidate from h and D, or a sentinel above 2^1000 that keeps the tag.
+template <bool AMGM>
+__device__ __forceinline__ double cand_tail(double h, double D, double thrM, int k, uint32_t msk)
+{
+    // sa ~ sqrt(D): v_rsq_f64 + one Newton step (sa = t + t*e/2)
+    const double r0 = __builtin_amdgcn_rsq(D);
+    const double tt = D * r0;
+    const double sa = fma(tt * 0.5, fma(-tt, r0, 1.0), tt);
+    const double n1 = -h - sa;
+    const bool r1 = n1 >= thrM;                     // n1 may reach 1e-4: hit_sphere takes t1
+    // the chosen root: n1 = -h - sa, or n2 = -h + sa; in the sphere-scene queue
+    // kernel (AMGM) as one fma with a selected sign (s * sa is exact; C2
+    // +0.7 %), elsewhere a select (the fma's constants cost the BVH
+    // instantiations registers: sweep -1.4 %)
+    const double n = AMGM ? fma(r1 ? -1.0 : 1.0, sa, -h) : (r1 ? n1 : sa - h);
+    // candidates: every chosen root that may reach 1e-4 (n >= thr - M),
+    // straddling ones included -- they are below any sure root, so
+    // the winner's own test after the scan (bn < thrP) catches them.
+    // n with its low 16 mantissa bits replaced by the slot (one
+    // v_and_or_b32; host: ns_cand <= 65534); |nt - n| < 2^-36 |n|
+    // <= 2^-34.4 Hs, inside M's slack
+    const double nt = cand_tag(n, k, msk);
+    return __hiloint2double(n >= thrM ? __double2hiint(nt) : 0x7fefffff, __double2loint(nt));
+}
+
+// MG: the flagged-pair loop is compiled in (every kernel whose cast is not
+// followed by a BVH walk, and rt_verify_sphere_pass; the BVH instantiations
+// keep the plain loop, which is right for any ns_merge -- with the flagged
+// loop their register allocation lost 0.7 % on C4)
+template <bool COUNT, bool CU, bool AMGM = false, bool MG = AMGM>
 __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, const V3 d, double a, double two_a,
                                                double four_a, bool fast, double rc2a, double& t_best, Cnt& cnt)
 {
@@ -181,7 +227,60 @@ __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, co
     double bn2 = __hiloint2double(0x7fefffff, -1);
     if (MN) bn = bn2;
     double gmin = bn2;                   // (MN) min |D| over the scan
-    for (int k = 0; k < kp.ns_cand; k += 2) {
+    // The records are in the host's order (rt_api.cpp order_candidates): the
+    // tag is the record's slot, and kp.sph_slot / kp.cand_orig give the
+    // winner's sphere.  The first ns_merge records are flagged pairs: spheres
+    // that a line rarely crosses both of, which share one root tail.
+    // A sphere with !(D > 0) only adds a sentinel: rsq of a non-positive D is
+    // NaN or inf, D * r0 and with it n is NaN, and n >= thrM fails.  Leaving
+    // that update out changes only the low bits of a sentinel in bn or bn2, and
+    // the decisions after the scan (any, bn2 - bn > M2, bk) only ask whether
+    // those are above 2^600; gmin takes both D either way.  So when no lane of
+    // the wave has both D > 0, one tail on each lane's own positive sphere (the
+    // first when neither is) gives what the two tails give; otherwise the two
+    // tails run.  The sign test reads D's high word: a positive D below 2^-1042
+    // counts as not positive, and is below T1 (>= 2^-177 on a fast ray: Hs >=
+    // 2^-20 sqrt(a), a >= 2^-101), where gmin makes the ray ambiguous.  The
+    // order and the flags are a hint: every order and every ns_merge give the
+    // same winner (tests/test_gpu_merged_tail.py, RT_CAND_MERGE).
+    // The flagged loop runs the first tail on each lane's choice (sphere 0
+    // unless the wave merges and the lane's D1 > 0; the choice goes into the
+    // tag's low bit, k being even) and the second tail only when the wave does
+    // not merge, updating bn and bn2 in place, so nothing has two definitions
+    // that meet at the latch (a v_mov_b64 each).  C2: 96 % of the flagged
+    // pairs' wave-casts merge, +1.6 % (profiles/r07_merge/).
+    int k = 0;
+    if (MN && MG) {
+        for (; k < kp.ns_merge; k += 2) {
+            double g[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) g[j] = sc[4 * k + j];
+            const double h0 = fma(-g[2], d.z, fma(-g[1], d.y, fma(-g[0], d.x, od)));
+            const double D0 = fma(h0, h0, -fma(g[2], oaz, fma(g[1], oay, fma(g[0], oax, fma(a, g[3], aoo)))));
+            double h1 = fma(-g[6], d.z, fma(-g[5], d.y, fma(-g[4], d.x, od)));
+            double D1 = fma(h1, h1, -fma(g[6], oaz, fma(g[5], oay, fma(g[4], oax, fma(a, g[7], aoo)))));
+            // (opaque to the compiler: paired up as two-element vectors, the two
+            // spheres cost a copy of every loop-invariant operand per cast)
+            asm("" : "+v"(h1), "+v"(D1));
+            gmin = dmin_abs2(dmin_abs2(gmin, D0), D1);
+            const int s0 = __double2hiint(D0), s1 = __double2hiint(D1);
+            const bool merged = __builtin_amdgcn_ballot_w64(min(s0, s1) > 0) == 0;
+#if RT_DIAG_MERGE
+            diag_merge()[merged ? 0 : 4] += 1u;
+#endif
+            const bool sel = merged && s1 > 0;
+            double nc = cand_tail<AMGM>(sel ? h1 : h0, sel ? D1 : D0, thrM, k, msk);
+            nc = __hiloint2double(__double2hiint(nc), __double2loint(nc) + (sel ? 1 : 0));
+            bn2 = dmin_raw(bn2, dmax_raw(bn, nc));
+            bn = dmin_raw(bn, nc);
+            if (!merged) {
+                const double nb = cand_tail<AMGM>(h1, D1, thrM, k + 1, msk);
+                dmin_acc(bn2, dmax_raw(bn, nb));
+                dmin_acc(bn, nb);
+            }
+        }
+    }
+    for (; k < kp.ns_cand; k += 2) {
         double g[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) g[j] = sc[4 * k + j];
@@ -194,43 +293,30 @@ __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, co
             // D finite here.  The ambiguity tests use xor of nested conditions
             // (a implies b: b && !a == a ^ b) so each comparison is issued once.
             // MN: one |D| < T1 test (grazing band widened from [-T2, T1) to
-            // (-T1, T1)); D <= -T1 gives a NaN root below, which no comparison
-            // accepts, so `valid` is implied by the candidate test
-            bool valid = true;
+            // (-T1, T1)); D <= -T1 gives a NaN root in cand_tail, which no
+            // comparison accepts, so `valid` is implied by the candidate test
             if (MN) {
                 gmin = dmin_abs2(gmin, D);                  // grazing test once, after the scan
-            } else {
-                valid = D >= T1;
-                amb = amb || (valid != (D >= nT2));         // -T2 <= D < T1: grazing
+                const double nc = cand_tail<AMGM>(h, D, thrM, k + e, msk);
+                bn2 = dmin_raw(bn2, dmax_raw(bn, nc));
+                bn = dmin_raw(bn, nc);
+                continue;
             }
+            const bool valid = D >= T1;
+            amb = amb || (valid != (D >= nT2));             // -T2 <= D < T1: grazing
             // sa ~ sqrt(D): v_rsq_f64 + one Newton step (sa = t + t*e/2)
             const double r0 = __builtin_amdgcn_rsq(D);
             const double tt = D * r0;
             const double sa = fma(tt * 0.5, fma(-tt, r0, 1.0), tt);
             const double n1 = -h - sa;
             const bool r1 = n1 >= thrM;                     // n1 may reach 1e-4: hit_sphere takes t1
-            // the chosen root: n1 = -h - sa, or n2 = -h + sa; in the sphere-scene queue
-            // kernel (AMGM) as one fma with a selected sign (s * sa is exact; C2
-            // +0.7 %), elsewhere a select (the fma's constants cost the BVH
-            // instantiations registers: sweep -1.4 %)
+            // the chosen root: n1 = -h - sa, or n2 = -h + sa (cand_tail)
             const double n = AMGM ? fma(r1 ? -1.0 : 1.0, sa, -h) : (r1 ? n1 : sa - h);
-            if (MN) {
-                // candidates: every chosen root that may reach 1e-4 (n >= thr - M),
-                // straddling ones included -- they are below any sure root, so
-                // the winner's own test after the scan (bn < thrP) catches them
-                const double nt = cand_tag(n, k + e, msk);
-                const double nc = __hiloint2double(n >= thrM ? __double2hiint(nt) : 0x7fefffff, __double2loint(nt));
-                bn2 = dmin_raw(bn2, dmax_raw(bn, nc));
-                bn = dmin_raw(bn, nc);
-                continue;
-            }
-            const double tP = CU ? (r1 ? thrP : thrP2) : thrP, tM = CU ? (r1 ? thrM : thrM2) : thrM;
+            const double tP = r1 ? thrP : thrP2, tM = r1 ? thrM : thrM2;
             const bool sure = n >= tP;
             amb = amb || (valid && (sure != (n >= tM)));    // the chosen root straddles 1e-4
             const bool cand = valid && sure;
-            // n with its low 16 mantissa bits replaced by the slot (one
-            // v_and_or_b32; host: ns_cand <= 65534); |nt - n| < 2^-36 |n|
-            // <= 2^-34.4 Hs, inside M's slack
+            // the slot in n's low 16 mantissa bits, as in cand_tail
             const double nt = cand_tag(n, k + e, msk);
             const double diff = nt - bn;
             const bool closer = cand && diff < -M2;
@@ -254,8 +340,9 @@ __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, co
     double t = INF;
     int win = -1;
     if (!amb && bk >= 0) {
-        const SphGeo s = kp.sph[bk];
-        if (sphere_exact<CU>(s.cx, s.cy, s.cz, s.r2, o, d, two_a, four_a, fast, rc2a, t)) win = bk;
+        const SphGeo s = kp.sph_slot[bk];    // the slot's sphere, and its index in the caller's list
+        const int orig = kp.cand_orig[bk];
+        if (sphere_exact<CU>(s.cx, s.cy, s.cz, s.r2, o, d, two_a, four_a, fast, rc2a, t)) win = orig;
         else amb = true;     // cannot happen within the bound; stay exact anyway
     }
     if (amb) {               // exact reference scan for this ray

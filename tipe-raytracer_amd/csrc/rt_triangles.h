@@ -450,7 +450,7 @@ __device__ __forceinline__ bool cuda_bbox(const KParams& kp, const V3 o, const V
 
 // The sphere half of closest_hit (and the cast counters): the winner index
 // or -1, its t in best (+inf when none).
-template <bool COUNT, bool CU, bool AMGM = false>
+template <bool COUNT, bool CU, bool AMGM = false, bool MG = AMGM>
 __device__ __forceinline__ int cast_spheres(const KParams& kp, const V3 o, const V3 d, double& best, Cnt& cnt)
 {
     const double a = dot(d, d);          // sphere.h:20 (same for every sphere)
@@ -464,7 +464,7 @@ __device__ __forceinline__ int cast_spheres(const KParams& kp, const V3 o, const
         cnt.c[RT_CNT_TRI_TESTS] += (unsigned long long)kp.nt;
         wave_slots(cnt, RT_CNT_CAST_LANE_SLOTS);
     }
-    int win = spheres_closest<COUNT, CU, AMGM>(kp, o, d, a, two_a, four_a, fast, rc2a, best, cnt);
+    int win = spheres_closest<COUNT, CU, AMGM, MG>(kp, o, d, a, two_a, four_a, fast, rc2a, best, cnt);
     return win;
 }
 
@@ -473,7 +473,8 @@ __device__ __forceinline__ int closest_hit(const KParams& kp, const V3 o, const 
                                            Cnt& cnt)
 {
     double best;
-    int win = cast_spheres<COUNT, CU, AMGM>(kp, o, d, best, cnt);
+    // the flagged-pair loop (spheres_closest MG) wherever no BVH walk follows
+    int win = cast_spheres<COUNT, CU, AMGM, AMGM || !BVH>(kp, o, d, best, cnt);
     int kind = win >= 0 ? HIT_SPHERE : HIT_NONE;
     int win_orig = 0;
     if (CU && kp.nt > 0 && !cuda_bbox(kp, o, d)) {
