@@ -1,7 +1,7 @@
 """The sphere candidate pass's merged root tail (rt_spheres.h spheres_closest):
 a flagged pair of spheres runs one tail in the wave-casts in which no lane's
 line crosses both, two otherwise.  Which pairs the host flags
-(rt_api.cpp order_candidates) is a hint, so every scene here must stay bit
+(rt_scene_prep.cpp order_candidates) is a hint, so every scene here must stay bit
 for bit on the oracle with the host's own flags and with every pair flagged
 in the caller's order (RT_CAND_MERGE=all), on the queue kernel
 (spp_chunks 32) and on the fixed grid (spp_chunks 1; both carry the

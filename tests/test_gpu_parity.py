@@ -814,7 +814,7 @@ def test_invalid_arguments_fail_loudly():
 
 @pytest.mark.parametrize("tw,th", [(16, 16), (3, 1), (64, 5), (1, 1)])
 def test_texel_map_fast_path_stress(tw, th):
-    """rt_verify_texel_map: the affine uv fast path (rt_api.cpp tri_uv_affine
+    """rt_verify_texel_map: the affine uv fast path (rt_scene_prep.cpp tri_uv_affine
     + tri_texel_affine) against the reference's barycentric operations on
     random triangles (scales 1e-3..1e2, far from the origin, skinny ones),
     random and grid-aligned uvs (boundaries through structured points, uv

@@ -1,0 +1,81 @@
+// rt_api_internal.h — what the C-ABI's files (rt_api.cpp, rt_drop_in.cpp,
+// rt_diag.cpp) share: error reporting, the device list, owning device memory
+// and the uploaded scene.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "rt/rt.h"
+#include "rt_internal.h"
+#include "rt_scene_prep.h"
+
+namespace rt {
+
+// Sets the calling thread's rt_last_error() text (one object for the whole
+// library, rt_api.cpp) and returns code.
+int fail(int code, const char* fmt, ...);
+
+#define HIP_TRY(expr)                                                                       \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess)                                                               \
+            return fail(RT_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                        __FILE__, __LINE__);                                                \
+    } while (0)
+
+// Restores the caller's current device on scope exit (torch owns it in bench).
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = false;
+    explicit DeviceGuard(int dev)
+    {
+        if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(dev) == hipSuccess) ok = true;
+    }
+    ~DeviceGuard()
+    {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// Device memory that is freed with its owner (on the device that is current
+// then).  Null until alloc/upload; an empty upload leaves it null.
+template <class T>
+struct DevArray {
+    T* p = nullptr;
+    DevArray() = default;
+    DevArray(const DevArray&) = delete;
+    DevArray& operator=(const DevArray&) = delete;
+    ~DevArray() { (void)hipFree(p); }
+    operator T*() const { return p; }
+    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, n * sizeof(T)); }
+    hipError_t upload(const T* src, size_t n)
+    {
+        if (n == 0) return hipSuccess;
+        const hipError_t e = alloc(n);
+        return e != hipSuccess ? e : hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice);
+    }
+};
+
+// The rt_init device list (device 0 when rt_init was not called), and its
+// first entry: where the diagnostics run.
+int device_list(std::vector<int>& devs);
+int first_device(int& dev);
+
+int validate_scene(const rt_scene* sc);
+int validate_params(const rt_params* p);
+
+void make_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling* t, KParams& kp, double* uni);
+int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count);
+void free_scene(rt_device_scene* s);
+
+// rt_drop_in.cpp, for rt_shutdown
+int scene_cache_clear();
+void stream_pool_clear();
+
+}  // namespace rt
+
+struct rt_device_scene : rt::SceneArrays<rt::DevArray> {
+    int device = 0;
+    rt::SceneFacts facts;
+};

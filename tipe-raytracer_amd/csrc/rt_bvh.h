@@ -1,5 +1,5 @@
 // rt_bvh.h — triangle BVH layout shared by the host builder (rt_bvh.cpp), the
-// C-ABI (rt_api.cpp) and the kernel (rt_kernels.hip, rt_triangles.h).
+// scene preparation (rt_scene_prep.cpp) and the kernel (rt_kernels.hip, rt_triangles.h).
 #pragma once
 #include <vector>
 

@@ -1,12 +1,13 @@
 // rt_internal.h — device-side scene layout and launch descriptors shared by
-// the C-ABI (rt_api.cpp) and the kernels (rt_kernels.hip and the headers it includes).
+// the C-ABI (rt_api.cpp; the scene's arrays are made by rt_scene_prep.cpp) and
+// the kernels (rt_kernels.hip and the headers it includes).
 //
 // HBM layout of one uploaded scene (DESIGN.md "Data layout"):
 //   SphCand [ns_pad] 32 B  center, |C|^2 - radius^2 — the candidate pass,
 //                          scanned wave-uniformly through the scalar unit,
 //                          two records per s_load_dwordx16; padded to an even
 //                          count with never-hit records (k = +inf); in the
-//                          host's pairing order (rt_api.cpp order_candidates)
+//                          host's pairing order (rt_scene_prep.cpp order_candidates)
 //   int     [ns_pad]       the sphere index of each candidate record, and
 //   SphGeo  [ns_pad]       its SphGeo (the candidate pass's winner)
 //   SphGeo  [ns_pad] 32 B  center, radius^2 — the exact reference test
@@ -62,7 +63,7 @@ static_assert(sizeof(SphCand) == 32, "SphCand");
 static_assert(sizeof(DevMat) == 80, "DevMat");
 static_assert(sizeof(TriGeo) == 96, "TriGeo");
 static_assert(sizeof(TriTex) == 136, "TriTex");
-// tri_uvmapping's u, v as affine functions of the hit point (rt_api.cpp
+// tri_uvmapping's u, v as affine functions of the hit point (rt_scene_prep.cpp
 // tri_uv_affine): u(P) = u0 + gu.(P - A), v(P) = v0 + gv.(P - A), with
 // tw*|u_ref - u| <= eu (th*|v_ref - v| <= ev) for every P within diam
 // (max-norm) of A, u_ref being the reference's rounded u; diam < 0: no fast
@@ -158,7 +159,7 @@ struct KParams {
     float bvh_rb_f;          // a float with rb_f (1 + 2^-23) <= R_b (the walk's cheap "inside" test)
     int bvh_far;             // some ray origin may lie beyond R_b: a sphere or the camera does
     int ns_merge;            // the first ns_merge (even) candidate records are pairs that may share one
-                             // root tail (rt_api.cpp order_candidates; a hint, any value gives the same result)
+                             // root tail (rt_scene_prep.cpp order_candidates; a hint, any value gives the same result)
     const int* cand_orig;    // [ns_pad] candidate record (slot) j describes sphere cand_orig[j] of sph
     const SphGeo* sph_slot;  // [ns_pad] sph[cand_orig[j]]: the candidate pass's winner retest
 };

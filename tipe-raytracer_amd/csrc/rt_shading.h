@@ -20,7 +20,7 @@ __device__ __forceinline__ V3 tri_normal(const KParams& kp, int k)
     const TriTex* t = kp.tri_tex + k;
     return v3(t->unx, t->uny, t->unz);
 }
-// The texel through the host's affine uv map (rt_api.cpp tri_uv_affine): the
+// The texel through the host's affine uv map (rt_scene_prep.cpp tri_uv_affine): the
 // reference's u, v are affine in P up to rounding, so with tw*u within eu of tu,
 // x = floor(tw u_ref) - tw floor(u_ref) is certain when no integer lies in
 // [tu - eu, tu + eu] (the wrap at integer u and the cells at multiples of 1/tw

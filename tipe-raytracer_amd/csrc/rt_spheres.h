@@ -227,7 +227,7 @@ __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, co
     double bn2 = __hiloint2double(0x7fefffff, -1);
     if (MN) bn = bn2;
     double gmin = bn2;                   // (MN) min |D| over the scan
-    // The records are in the host's order (rt_api.cpp order_candidates): the
+    // The records are in the host's order (rt_scene_prep.cpp order_candidates): the
     // tag is the record's slot, and kp.sph_slot / kp.cand_orig give the
     // winner's sphere.  The first ns_merge records are flagged pairs: spheres
     // that a line rarely crosses both of, which share one root tail.

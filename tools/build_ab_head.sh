@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build tools/variants/a_head.so from git HEAD (a scratch worktree) and
-# tools/variants/b_work.so from the working tree, for tools/ab_*.sh.
+# tools/variants/b_work.so from the working tree, each with its own tree's
+# Makefile (so each links its own source list), for RT_HIP_LIB A/B runs.
 #   bash tools/build_ab_head.sh [ref]
 set -e
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
@@ -9,10 +10,9 @@ WT=/tmp/rt_ab_head
 rm -rf "$WT"; git -C "$ROOT" worktree prune
 git -C "$ROOT" worktree add -f --detach "$WT" "$REF" >/dev/null
 mkdir -p "$ROOT/tools/variants"; rm -f "$ROOT"/tools/variants/*.so
-F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I../include -Icsrc -shared csrc/rt_kernels.hip csrc/rt_api.cpp csrc/rt_bvh.cpp"
-src() { [ -f "$1/tipe-raytracer_amd/csrc/rt_rccl.cpp" ] && echo "csrc/rt_rccl.cpp -ldl"; }   # r06 on
-(cd "$WT/tipe-raytracer_amd" && /opt/rocm/bin/hipcc $F $(src "$WT") -o "$ROOT/tools/variants/a_head.so") &
-(cd "$ROOT/tipe-raytracer_amd" && /opt/rocm/bin/hipcc $F $(src "$ROOT") -o "$ROOT/tools/variants/b_work.so") &
-wait
+build() { make -s -C "$1/tipe-raytracer_amd" librt_hip.so && cp "$1/tipe-raytracer_amd/librt_hip.so" "$ROOT/tools/variants/$2.so"; }
+build "$WT" a_head & A=$!
+build "$ROOT" b_work & B=$!
+wait $A; wait $B
 git -C "$ROOT" worktree remove --force "$WT"
 ls "$ROOT/tools/variants"
