@@ -159,7 +159,9 @@ typedef struct rt_params {
  * rt_scene_upload and closest-hit traverses it (the hit chosen is still the
  * reference's: the lexicographic minimum of (dst, triangle index) over the
  * same exact tests, DESIGN.md "BVH"); NONE: test every triangle, as
- * main.c:80-90. */
+ * main.c:80-90.  The BVH serves meshes of up to 2^24 (16 777 216) triangles;
+ * above 65535 triangles it is a "wide" tree with kernels of its own (below).
+ * A larger mesh is accepted and rendered by testing every triangle. */
 #define RT_ACCEL_AUTO 0
 #define RT_ACCEL_NONE 1
 
@@ -224,7 +226,9 @@ int rt_abi_version(void);
  * sphere-only instantiations (-2: every material opaque); "<QB=3,OP>" = the
  * deep-tree one for scenes whose every material is opaque;
  * "render_kernel<BVH>" / "render_kernel" = the fixed-grid kernels,
- * "render_kernel_cuda"); "none" before the first.
+ * "render_kernel_cuda"; for a wide tree -- a mesh above 65535 triangles --
+ * "render_kernel_q<QB=5>" = the task-queue kernel and
+ * "render_kernel<BVH32>" = the fixed-grid one); "none" before the first.
  * The choice never changes a result.  Diagnostics and tests. */
 const char* rt_last_render_kernel(void);
 const char* rt_version(void);

@@ -187,7 +187,6 @@ void make_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling
     kp.sph_disp = sc->sph_disp;
     kp.tri_mat = sc->tri_mat;
     kp.cuda = p->semantics == RT_SEM_CUDA ? 1 : 0;
-    kp.f32 = 0;                      // (RT_PREC_FP32 removed in r05; the field keeps the kernarg layout)
     for (int i = 0; i < 6; ++i) kp.cbb[i] = f.cbb[i];
     if (p->sky_mode == RT_SKY_LAST_SPHERE && sc->sky && f.ns > 0) {
         kp.sky = sc->sky;
@@ -284,6 +283,13 @@ void make_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling
         // need (rt_bvh.cpp's exact bound), or more than any stack when an index
         // would not fit
         kp.bvh_stack = (f.bvh_nodes < 0x8000 && f.nt <= 0x8000) ? f.bvh_stack4 : 1 << 30;
+        // a wide tree (rt_bvh.h): 32-bit stacks and the wide 64-byte nodes, so
+        // its exact bound always counts; it has no BvhNodeH form
+        if (f.bvh_wide) {
+            kp.bvh_wide = 1;
+            kp.bvhw = sc->bvhw;
+            kp.bvh_stack = f.bvh_stack4;
+        }
         // shallow trees finish most walks in one round with 4 visits; deeper ones
         // do best with 3 (measured: sweep depth4 3: 3395 -> 3542 at 4; C4 depth4 7:
         // 1134 at 3, 1122 at 4)
@@ -453,7 +459,7 @@ int rt_scene_upload(int device, const rt_scene* scene, rt_device_scene** out)
     if ((rc = upload(ds->sph, hs.sph)) || (rc = upload(ds->sph_cand, hs.sph_cand)) || (rc = upload(ds->cand_orig, hs.cand_orig)) ||
         (rc = upload(ds->sph_slot, hs.sph_slot)) || (rc = upload(ds->sph_mat, hs.sph_mat)) || (rc = upload(ds->tri, hs.tri)) ||
         (rc = upload(ds->tri_tex, hs.tri_tex)) || (rc = upload(ds->tri_uv, hs.tri_uv)) || (rc = upload(ds->texels, hs.texels)) ||
-        (rc = upload(ds->bvh, hs.bvh)) || (rc = upload(ds->bvhh, hs.bvhh)) || (rc = upload(ds->tri_orig, hs.tri_orig)) ||
+        (rc = upload(ds->bvh, hs.bvh)) || (rc = upload(ds->bvhh, hs.bvhh)) || (rc = upload(ds->bvhw, hs.bvhw)) || (rc = upload(ds->tri_orig, hs.tri_orig)) ||
         (rc = upload(ds->sky, hs.sky)) || (rc = upload(ds->sph_rinv, hs.sph_rinv)) || (rc = upload(ds->sph_disp, hs.sph_disp)) ||
         (rc = upload(ds->tri_mat, hs.tri_mat))) {
         free_scene(ds);

@@ -7,7 +7,9 @@
 // of BOTH children (float, rounded outward), so one 64-byte node fetch
 // decides both descents.  Node 0
 // is the root split; triangles are reordered into leaf order and the kernel
-// keeps each one's original index for the reference's tie-break.
+// keeps each one's original index for the reference's tie-break.  Meshes of
+// up to 2^24 triangles; above 65535 the tree is "wide" (rt_bvh.h): its leaves
+// are renumbered breadth-first and its 64-byte nodes are BvhNodeW.
 //
 // Exactness: the BVH only decides which triangles are *tested*; every test
 // is the reference arithmetic and the winner is the lexicographic minimum of
@@ -261,13 +263,16 @@ double bvh_origin_radius(const TriGeo* tri, int nt, double tri_bound, const doub
 bool build_bvh(const TriGeo* tri, int nt, double r_scene, BvhBuild& out)
 {
     out = BvhBuild();
-    if (const char* e = std::getenv("RT_BVH_LEAF")) kLeaf = std::max(1, std::min(16, std::atoi(e)));
+    const char* e = std::getenv("RT_BVH_LEAF");          // read per build: unset means 1 again
+    kLeaf = e ? std::max(1, std::min(16, std::atoi(e))) : 1;
     if (nt <= kLeaf) return false;
-    // The SAH build makes leaves of kLeaf triangles except where the depth cap
-    // binds, so a mesh of more than 65535 * kLeaf triangles gets >= 65535
-    // internal nodes, which the uint16 traversal stack entries refuse (checked
-    // again below): refuse before paying for the sweep build.
-    if ((nt + kLeaf - 1) / kLeaf - 1 >= 65535) return false;
+    // Index limits (rt_bvh.h kMaxTris): 32-bit byte offsets k * sizeof(TriGeo),
+    // k * sizeof(TriTex) and node * 128 below 2^32, samples_coop's lane |
+    // node << 6 in 32 bits, 24-bit stack entries in the QB 5 kernel.  A binary
+    // tree over nt triangles has at most nt - 1 nodes and the 4-wide one no
+    // more, so nt <= 2^24 keeps every index inside all of them: refuse before
+    // paying for the sweep build.
+    if (nt > kMaxTris) return false;
     double maxN = 0.0;
     std::vector<Prim> P((size_t)nt);
     for (int i = 0; i < nt; ++i) {
@@ -293,7 +298,7 @@ bool build_bvh(const TriGeo* tri, int nt, double r_scene, BvhBuild& out)
     }
     Builder bld{P, out.nodes};
     const Ref root = bld.build(0, nt, 0);
-    if (root.leaf || out.nodes.size() >= 65535) {        // uint16 traversal stack entries
+    if (root.leaf) {
         out = BvhBuild();
         return false;
     }
@@ -341,9 +346,32 @@ bool build_bvh(const TriGeo* tri, int nt, double r_scene, BvhBuild& out)
         }
         out.stack4 = need.empty() ? 0 : need[0];
     }
-    if (out.stack4 > kStack4 || out.nodes4.size() >= 65535) {
+    if (out.stack4 > kStack4) {
         out = BvhBuild();
         return false;
+    }
+    // A wide tree (rt_bvh.h kNarrowMax) stores its triangles in the
+    // breadth-first order of the leaves, slot order within a node, so that a
+    // node's leaf children are consecutive from its first one (BvhNodeW's
+    // tri_base).  The reference's tie rule reads the original index (order),
+    // so the storage order is free; narrow trees keep the build's order.
+    out.wide = nt > kNarrowMax || out.nodes.size() >= (size_t)kNarrowMax || out.nodes4.size() >= (size_t)kNarrowMax;
+    if (out.wide) {
+        std::vector<int> moved((size_t)nt, -1);  // old first triangle of a leaf -> new
+        std::vector<int> order((size_t)nt);
+        int next = 0;
+        for (BvhNode4& nd : out.nodes4)
+            for (int c = 0; c < 4; ++c) {
+                if (nd.count[c] <= 0) continue;
+                for (int j = 0; j < nd.count[c]; ++j) order[(size_t)(next + j)] = out.order[(size_t)(nd.child[c] + j)];
+                moved[(size_t)nd.child[c]] = next;
+                nd.child[c] = next;
+                next += nd.count[c];
+            }
+        for (BvhNode& nd : out.nodes)
+            for (int c = 0; c < 2; ++c)
+                if (nd.count[c] > 0) nd.child[c] = moved[(size_t)nd.child[c]];
+        out.order.swap(order);
     }
     const double k = std::ldexp(1e6, -44) * maxN;
     out.s_rel = k + std::ldexp(1.0, -48);
@@ -411,6 +439,61 @@ bool h_round(double x, bool up, unsigned short& h)
     return true;
 }
 
+// The fields BvhNodeH and BvhNodeW share: the binary16 origin, the planes
+// relative to it (rounded outward) and the count nibbles of one node.  rb
+// grows to >= |org| + |plane|.  false: beyond binary16's range, or a leaf of
+// more than 14 triangles.
+template <class Node>
+bool pack_planes(const BvhNode4& n, Node& h, double& rb)
+{
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL};
+    for (int c = 0; c < 4; ++c)
+        if (n.count[c] >= 0)
+            for (int a = 0; a < 3; ++a) lo[a] = std::fmin(lo[a], (double)n.lo[a][c]);
+    double org[3];
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(lo[a])) lo[a] = 0.0;
+        if (!h_round(lo[a], false, h.org[a])) return false;
+        org[a] = h2d(h.org[a]);
+        rb = std::fmax(rb, std::fabs(org[a]));
+    }
+    h.cnt = 0;
+    for (int c = 0; c < 4; ++c) {
+        int nib;
+        if (n.count[c] < 0) nib = 15;
+        else if (n.count[c] > 14) return false;
+        else nib = n.count[c];
+        h.cnt = (unsigned short)(h.cnt | (nib << (4 * c)));
+        for (int a = 0; a < 3; ++a) {
+            if (n.count[c] < 0) {
+                h.plo[a][c] = h.phi[a][c] = 0;
+                continue;
+            }
+            // org + rel in double is exact (two binary16 values), so the
+            // comparisons below are exact; step outward until they hold
+            unsigned short ql, qh;
+            if (!h_round((double)n.lo[a][c] - org[a], false, ql) || !h_round((double)n.hi[a][c] - org[a], true, qh))
+                return false;
+            while (org[a] + h2d(ql) > (double)n.lo[a][c])
+                if (!h_down(ql)) return false;
+            while (org[a] + h2d(qh) < (double)n.hi[a][c])
+                if (!h_up(qh)) return false;
+            h.plo[a][c] = ql;
+            h.phi[a][c] = qh;
+            rb = std::fmax(rb, std::fmax(std::fabs(org[a] + h2d(ql)), std::fabs(org[a] + h2d(qh))));
+            rb = std::fmax(rb, std::fabs(org[a]) + std::fmax(std::fabs(h2d(ql)), std::fabs(h2d(qh))));
+        }
+    }
+    return true;
+}
+
+bool rbox_of(double rb, float& rbox)
+{
+    rbox = (float)rb;
+    if ((double)rbox < rb) rbox = std::nextafter(rbox, HUGE_VALF);
+    return std::isfinite(rbox);
+}
+
 }  // namespace
 
 bool pack_bvh_h(const std::vector<BvhNode4>& nodes4, std::vector<BvhNodeH>& out, float& rbox)
@@ -420,50 +503,41 @@ bool pack_bvh_h(const std::vector<BvhNode4>& nodes4, std::vector<BvhNodeH>& out,
     for (size_t i = 0; i < nodes4.size(); ++i) {
         const BvhNode4& n = nodes4[i];
         BvhNodeH& h = out[i];
-        double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL};
-        for (int c = 0; c < 4; ++c)
-            if (n.count[c] >= 0)
-                for (int a = 0; a < 3; ++a) lo[a] = std::fmin(lo[a], (double)n.lo[a][c]);
-        double org[3];
-        for (int a = 0; a < 3; ++a) {
-            if (!std::isfinite(lo[a])) lo[a] = 0.0;
-            if (!h_round(lo[a], false, h.org[a])) return false;
-            org[a] = h2d(h.org[a]);
-            rb = std::fmax(rb, std::fabs(org[a]));
-        }
-        h.cnt = 0;
+        if (!pack_planes(n, h, rb)) return false;
         for (int c = 0; c < 4; ++c) {
-            int nib;
-            if (n.count[c] < 0) nib = 15;
-            else if (n.count[c] > 14) return false;
-            else nib = n.count[c];
             if (n.count[c] >= 0 && (n.child[c] < 0 || n.child[c] > 0xffff)) return false;
-            h.cnt = (unsigned short)(h.cnt | (nib << (4 * c)));
             h.child[c] = (unsigned short)(n.count[c] >= 0 ? n.child[c] : 0);
-            for (int a = 0; a < 3; ++a) {
-                if (n.count[c] < 0) {
-                    h.plo[a][c] = h.phi[a][c] = 0;
-                    continue;
-                }
-                // org + rel in double is exact (two binary16 values), so the
-                // comparisons below are exact; step outward until they hold
-                unsigned short ql, qh;
-                if (!h_round((double)n.lo[a][c] - org[a], false, ql) || !h_round((double)n.hi[a][c] - org[a], true, qh))
-                    return false;
-                while (org[a] + h2d(ql) > (double)n.lo[a][c])
-                    if (!h_down(ql)) return false;
-                while (org[a] + h2d(qh) < (double)n.hi[a][c])
-                    if (!h_up(qh)) return false;
-                h.plo[a][c] = ql;
-                h.phi[a][c] = qh;
-                rb = std::fmax(rb, std::fmax(std::fabs(org[a] + h2d(ql)), std::fabs(org[a] + h2d(qh))));
-                rb = std::fmax(rb, std::fabs(org[a]) + std::fmax(std::fabs(h2d(ql)), std::fabs(h2d(qh))));
+        }
+    }
+    return rbox_of(rb, rbox);
+}
+
+bool pack_bvh_w(const std::vector<BvhNode4>& nodes4, std::vector<BvhNodeW>& out, float& rbox)
+{
+    out.assign(nodes4.size(), BvhNodeW{});
+    double rb = 0.0;
+    for (size_t i = 0; i < nodes4.size(); ++i) {
+        const BvhNode4& n = nodes4[i];
+        BvhNodeW& w = out[i];
+        if (!pack_planes(n, w, rb)) return false;
+        // the bases are the first internal / leaf child's index; every later
+        // one must sit where the kernel's prefix sums put it (box4w)
+        long long node_next = -1, tri_next = -1;
+        for (int c = 0; c < 4; ++c) {
+            if (n.count[c] < 0) continue;
+            if (n.child[c] < 0 || n.child[c] >= kMaxTris) return false;
+            if (n.count[c] == 0) {
+                if (node_next < 0) w.node_base = (unsigned)n.child[c];
+                else if (n.child[c] != node_next) return false;
+                node_next = (long long)n.child[c] + 1;
+            } else {
+                if (tri_next < 0) w.tri_base = (unsigned)n.child[c];
+                else if (n.child[c] != tri_next) return false;
+                tri_next = (long long)n.child[c] + n.count[c];
             }
         }
     }
-    rbox = (float)rb;
-    if ((double)rbox < rb) rbox = std::nextafter(rbox, HUGE_VALF);
-    return std::isfinite(rbox);
+    return rbox_of(rb, rbox);
 }
 
 }  // namespace rt

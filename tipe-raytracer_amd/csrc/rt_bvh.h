@@ -61,10 +61,45 @@ static_assert(sizeof(BvhNodeH) == 64, "BvhNodeH");
 // margin's coordinate bound for the packed planes).
 bool pack_bvh_h(const std::vector<BvhNode4>& nodes4, std::vector<BvhNodeH>& out, float& rbox);
 
+// The 64-byte node of a wide tree (BvhBuild::wide: some node or triangle index
+// exceeds 65535), for the queue kernel's QB 5 instantiation: planes, origin
+// and counts as BvhNodeH's, and in place of the four 16-bit child indices two
+// 32-bit bases.  build_bvh numbers the nodes breadth-first and pushes a node's
+// internal children in slot order, and it stores a wide tree's triangles in
+// the breadth-first order of the leaves (slot order within a node), so
+//   internal child c = node_base + (internal slots before c)
+//   leaf child c     = triangles [tri_base + (counts of the leaf slots before c), + count)
+struct BvhNodeW {
+    unsigned short plo[3][4];
+    unsigned short phi[3][4];
+    unsigned short org[3];
+    unsigned short cnt;             // count of child c in bits 4c..4c+3 (as BvhNodeH)
+    unsigned node_base, tri_base;
+};
+static_assert(sizeof(BvhNodeW) == 64, "BvhNodeW");
+
+// Packs a wide tree's nodes4 into BvhNodeW; false as pack_bvh_h (binary16's
+// range, a leaf of more than 14 triangles) or when the children are not
+// numbered as above.  rbox as pack_bvh_h's.
+bool pack_bvh_w(const std::vector<BvhNode4>& nodes4, std::vector<BvhNodeW>& out, float& rbox);
+
+// Index limits of a tree (build_bvh refuses beyond them; nodes <= triangles - 1):
+//  * 32-bit byte offsets from the arrays' bases: k * sizeof(TriGeo) (96),
+//    k * sizeof(TriTex) (136) and node * sizeof(BvhNode4) (128) stay below
+//    2^32 for k, node < 2^24 (136 * 2^24 < 2^32);
+//  * samples_coop's LIFO items pack lane | node << 6 into 32 bits: node < 2^26;
+//  * the QB 5 kernel's stack entries hold 24 bits: node < 2^24.
+constexpr int kMaxTris = 1 << 24;
+// The narrow forms (uint16 stack entries, BvhNodeH's 16-bit child indices)
+// serve trees of at most kNarrowMax triangles and fewer than kNarrowMax nodes
+// (binary and 4-wide); every other tree is wide (BvhBuild::wide).
+constexpr int kNarrowMax = 65535;
+
 struct BvhBuild {
     std::vector<BvhNode> nodes;     // binary tree, node 0 = root split
     std::vector<BvhNode4> nodes4;   // collapsed 4-wide tree, node 0 = root
     std::vector<int> order;         // leaf order -> original triangle index
+    bool wide = false;              // a node or triangle index exceeds 65535: 32-bit stacks, BvhNodeW
     int depth = 0;                  // binary depth
     int depth4 = 0;                 // 4-wide depth
     int stack4 = 0;                 // traversal stack entries the tree can need (<= 3 * depth4; <= kStack4)
@@ -77,8 +112,8 @@ struct BvhBuild {
 // Builds over nt precomputed triangles whose coordinates are bounded by
 // r_scene in magnitude; the padding assumes ray origins within r_scene too,
 // and the walk widens it per ray for origins beyond (k_delta, rt_triangles.h
-// ray32).  false: no BVH (too few triangles or too many nodes) -> brute-force
-// scan.
+// ray32).  false: no BVH (too few triangles, more than kMaxTris, or a stack
+// bound above kStack4) -> brute-force scan.
 bool build_bvh(const TriGeo* tri, int nt, double r_scene, BvhBuild& out);
 // >= d(padding)/dR of every triangle (BvhBuild::k_delta); median_e: the
 // median e1 + e2 (may be null).

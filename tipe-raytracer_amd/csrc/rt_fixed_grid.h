@@ -10,13 +10,13 @@ namespace rt {
 // hit (the COUNT build recasts it, to count what main_cuda.cu casts); no
 // alpha holes, refraction, textures or x1.3 brightening; a triangle's
 // material is its own (kp.tri_mat); albedo/normal are the pre-pass hit's.
-template <bool COUNT, bool BVH>
+template <bool COUNT, bool BVH, class SE = unsigned short>
 __device__ __forceinline__ bool cuda_hit(const KParams& kp, const V3 o, const V3 d, V3& hp, V3& hn, Mat& mat,
                                          Cnt& cnt)
 {
     double t;
     int idx;
-    const int kind = closest_hit<COUNT, BVH, true>(kp, o, d, t, idx, cnt);
+    const int kind = closest_hit<COUNT, BVH, true, false, SE>(kp, o, d, t, idx, cnt);
     if (kind == HIT_NONE) return false;
     hp = o + muls(d, t);                                 // ray_at
     if (kind == HIT_SPHERE) {
@@ -30,12 +30,12 @@ __device__ __forceinline__ bool cuda_hit(const KParams& kp, const V3 o, const V3
     return true;
 }
 
-template <bool COUNT, bool BVH>
+template <bool COUNT, bool BVH, class SE = unsigned short>
 __device__ __forceinline__ void trace_cuda(const KParams& kp, V3 o, V3 d, Stream& st, double* acc, Cnt& cnt)
 {
     V3 hp, hn;
     Mat mat;
-    if (!cuda_hit<COUNT, BVH>(kp, o, d, hp, hn, mat, cnt)) {    // return BLACK
+    if (!cuda_hit<COUNT, BVH, SE>(kp, o, d, hp, hn, mat, cnt)) {    // return BLACK
         acc_add(acc, ACC_RAD, v3(0, 0, 0));
         acc_add(acc, ACC_ALB, v3(0, 0, 0));
         acc_add(acc, ACC_NRM, v3(0, 0, 0));
@@ -52,7 +52,7 @@ __device__ __forceinline__ void trace_cuda(const KParams& kp, V3 o, V3 d, Stream
     acc_add(acc, ACC_NRM, hn);
     V3 inc = v3(0, 0, 0), rc = v3(1, 1, 1);
     for (int i = 0; i < kp.B; i++) {
-        if ((i > 0 || COUNT) && !cuda_hit<COUNT, BVH>(kp, o, d, hp, hn, mat, cnt)) break;
+        if ((i > 0 || COUNT) && !cuda_hit<COUNT, BVH, SE>(kp, o, d, hp, hn, mat, cnt)) break;
         o = hp;
         const V3 diffuse_dir = normalize(hn + random_dir<COUNT>(st, cnt));
         const V3 reflected_dir = d - muls(hn, 2 * dot(d, hn));
@@ -62,7 +62,7 @@ __device__ __forceinline__ void trace_cuda(const KParams& kp, V3 o, V3 d, Stream
             const V3 em = muls(mat.emis, mat.es * 1.5 * AO);
             inc = inc + mulv(em, rc);
             rc = mulv(mat.diff, rc);
-            const double occ = ao_factor<COUNT, BVH, true>(kp, hp, hn, AO, st, cnt);
+            const double occ = ao_factor<COUNT, BVH, true, SE>(kp, hp, hn, AO, st, cnt);
             rc = mulv(rc, v3(occ, occ, occ));
         } else {
             const V3 em = muls(mat.emis, mat.es);
@@ -375,7 +375,8 @@ struct LanePath {
     }
 
     // up to k node visits; RESOLVE when the traversal is over
-    __device__ __forceinline__ void trav(const KParams& kp, unsigned short* stk, int k, Cnt& cnt)
+    template <class SE>
+    __device__ __forceinline__ void trav(const KParams& kp, SE* stk, int k, Cnt& cnt)
     {
 #pragma unroll 1
         for (int j = 0; j < k; ++j) {
@@ -466,9 +467,9 @@ __device__ __forceinline__ void lifo_push(volatile unsigned* q, int& cnt, int n,
 // One node visit of a cooperative task: as bvh_step, but hit internal
 // children other than the next one go to push[] (for the LIFO) when
 // to_lifo, else on the lane's own stack.  hit: a triangle beat the record.
-template <bool COUNT>
+template <bool COUNT, class SE>
 __device__ __forceinline__ bool coop_step(const KParams& kp, const V3 o, const V3 d, const Ray32& r32,
-                                          unsigned short* stk, int& node, int& sp, double& best, int& kind,
+                                          SE* stk, int& node, int& sp, double& best, int& kind,
                                           int& win, int& win_orig, bool& hit, bool to_lifo, unsigned* push,
                                           int& npush, Cnt& cnt)
 {
@@ -506,7 +507,7 @@ __device__ __forceinline__ bool coop_step(const KParams& kp, const V3 o, const V
             } else {
                 if (COUNT && sp >= kp.stack_cap) cnt.c[RT_CNT_BVH_STACK_OVER] += 1;
                 if (!COUNT || sp < kStack4) {
-                    stk[sp * 256] = (unsigned short)pu;
+                    stk_put(stk, sp, pu);
                     ++sp;
                 }
             }
@@ -533,18 +534,18 @@ __device__ __forceinline__ bool coop_step(const KParams& kp, const V3 o, const V
     }
     if (sp == 0) return false;
     --sp;
-    node = stk[sp * 256];
+    node = stk_get(stk, sp);
     return true;
 }
 
-template <bool COUNT, bool SKY>
+template <bool COUNT, bool SKY, class SE = unsigned short>
 __device__ __forceinline__ void samples_coop(const KParams& kp, int x, int g, uint32_t pixel, int s0, int s1,
                                              uint32_t* rng, double* acc, Cnt& cnt)
 {
     constexpr int QW = 256;                      // < 64 entries + 3 pushes x 64 lanes
     __shared__ unsigned lifo_lds[4][QW];
     volatile unsigned* q = lifo_lds[threadIdx.x >> 6];
-    unsigned short* stk = bvh_stack();
+    SE* stk = bvh_stack_of<SE>();
     const int lane = threadIdx.x & 63;
     LanePath<COUNT, SKY> L;
     L.init(s0, s1);
@@ -566,7 +567,7 @@ __device__ __forceinline__ void samples_coop(const KParams& kp, int x, int g, ui
             int n = 0;
             if (L.state == SM_TRAV) {            // next node + the root's pushes (sp <= 3)
                 it[0] = (unsigned)lane | ((unsigned)L.node << 6);
-                for (int j = 0; j < L.sp; ++j) it[1 + j] = (unsigned)lane | ((unsigned)stk[j * 256] << 6);
+                for (int j = 0; j < L.sp; ++j) it[1 + j] = (unsigned)lane | ((unsigned)stk_get(stk, j) << 6);
                 n = 1 + L.sp;
             }
             lifo_push(q, qn, n, it);
@@ -611,7 +612,7 @@ __device__ __forceinline__ void samples_coop(const KParams& kp, int x, int g, ui
             int npush = 0;
             const bool to_lifo = qn < 64;
             if (has) {
-                if (!coop_step<COUNT>(kp, to, td, tr32, stk, tnode, tsp, best, kind, win, win_orig, hit, to_lifo,
+                if (!coop_step<COUNT, SE>(kp, to, td, tr32, stk, tnode, tsp, best, kind, win, win_orig, hit, to_lifo,
                                       push, npush, cnt))
                     has = false;
 #pragma unroll
@@ -669,7 +670,8 @@ __device__ __forceinline__ int chunk_start(int S, int chunks, int taper, unsigne
 
 // Body of render_kernel (main.c semantics) and render_kernel_cuda
 // (main_cuda.cu's): one thread = (pixel, chunk of its samples).
-template <bool COUNT, bool BVH, bool SKY, bool CU>
+// SE: the BVH stack's element type (uint32_t: a wide tree, rt_bvh.h)
+template <bool COUNT, bool BVH, bool SKY, bool CU, class SE = unsigned short>
 __device__ __forceinline__ void render_body(const KParams& kp)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -700,7 +702,7 @@ __device__ __forceinline__ void render_body(const KParams& kp)
 #pragma unroll
         for (int j = 0; j < 9; ++j) acc[j * 256] = carry ? kp.sums[li * 9 + j] : 0.0;
         if constexpr (BVH && !CU) {
-            samples_coop<COUNT, SKY>(kp, x, g, pixel, s0, s1, rng_lds + threadIdx.x, acc, cnt);
+            samples_coop<COUNT, SKY, SE>(kp, x, g, pixel, s0, s1, rng_lds + threadIdx.x, acc, cnt);
         } else if constexpr (!BVH && !CU) {
             samples_flat<COUNT, SKY>(kp, x, g, pixel, s0, s1, rng_lds + threadIdx.x, acc, cnt);
         } else {                             // CU: main_cuda.cu's nested sample loop (main_cuda.cu:150-165)
@@ -709,7 +711,7 @@ __device__ __forceinline__ void render_body(const KParams& kp)
                 st.start(pixel, (uint32_t)(kp.s_base + s), kp.key0, kp.key1, rng_lds + threadIdx.x);
                 V3 no, rd;
                 camera_ray<CU>(kp, x, g, st, no, rd);
-                trace_cuda<COUNT, BVH>(kp, no, rd, st, acc, cnt);
+                trace_cuda<COUNT, BVH, SE>(kp, no, rd, st, acc, cnt);
                 if (COUNT) {
                     cnt.c[RT_CNT_SAMPLES] += 1;
                     cnt.c[RT_CNT_RNG_DRAWS] += st.n;
@@ -756,6 +758,23 @@ __global__ __launch_bounds__(256, BVH ? RT_WAVES_PER_SIMD_BVH : RT_WAVES_PER_SIM
     const KParams kp)
 {
     render_body<COUNT, BVH, false, true>(kp);
+}
+
+// The same two kernels for a wide tree (rt_bvh.h BvhBuild::wide: node or
+// triangle indices beyond 16 bits): the walk of the 128-byte nodes, whose
+// children are ints, with uint32 stack entries (bvh_stack32: 48 KiB, two
+// blocks per CU).  The universal path of wide trees: spp_chunks 1,
+// rt_accumulate_async, rt_count_async, RT_SEM_CUDA, trees whose 64-byte form
+// does not pack or whose stack bound exceeds the queue kernel's.
+template <bool COUNT, bool SKY>
+__global__ __launch_bounds__(256, 2) void render_kernel_w(const KParams kp)
+{
+    render_body<COUNT, true, SKY, false, uint32_t>(kp);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(256, 2) void render_kernel_cuda_w(const KParams kp)
+{
+    render_body<COUNT, true, false, true, uint32_t>(kp);
 }
 
 }  // namespace rt

@@ -18,6 +18,8 @@
 //   BvhNode4[nodes] 128 B  four child boxes (rt_bvh.h) when nt > 32; the
 //   int     [nt]           triangle arrays are then in leaf order and
 //                          tri_orig maps back to the caller's order
+//   BvhNodeH[nodes]  64 B  the same tree for the queue kernel, or, for a wide
+//   BvhNodeW[nodes]  64 B  tree (nt > 65535, rt_bvh.h), its form with 32-bit bases
 //   DevMat  [nm*th*tw]     texel table (reference `material` records)
 //   DevMat  [nt]           rt_triangle.mat per triangle (RT_SEM_CUDA materials)
 //   double  [ns][3]        the colour an emitting sphere shows when seen
@@ -32,6 +34,7 @@ namespace rt {
 
 struct BvhNode4;                                      // rt_bvh.h
 struct BvhNodeH;                                      // rt_bvh.h (64-byte form)
+struct BvhNodeW;                                      // rt_bvh.h (64-byte form of a wide tree)
 
 struct SphGeo { double cx, cy, cz, r2; };            // r2 = radius*radius (sphere.h:22)
 // Candidate-pass record (rt_spheres.h spheres_closest): center and
@@ -96,12 +99,17 @@ struct KParams {
     const DevMat* texels;
     const double* uni;       // U_COUNT doubles
     const BvhNode4* bvh;     // 4-wide triangle BVH (rt_bvh.h), or null: brute-force scan
-    const BvhNodeH* bvhh;    // the same tree in 64-byte nodes (the queue kernel's), or null
+    union {                  // the same tree in 64-byte nodes (the queue kernel's), or null: a tree has
+        const BvhNodeH* bvhh;    // one such form, BvhNodeH, or (bvh_wide) BvhNodeW, so the two share the
+        const BvhNodeW* bvhw;    // kernarg slot (a new field would move every kernel's argument size)
+    };
     const int* tri_orig;     // triangle k's index in the caller's list (null: k)
     const DevMat* sky;       // sky texels when sky mode is on, else null
     const DevMat* tri_mat;   // rt_triangle.mat per triangle (leaf order with a BVH): RT_SEM_CUDA
     int cuda;                // rt.h RT_SEM_CUDA (render_kernel_cuda)
-    int f32;                 // always 0: RT_PREC_FP32 was removed in r05 (field kept: kernarg layout)
+    int bvh_wide;            // the tree is wide (rt_bvh.h: node or triangle indices beyond 16 bits): only the
+                             // kernels with wider stack entries may walk it, and its 64-byte form is bvhw
+                             // (the slot of r05's removed RT_PREC_FP32 flag)
     double cbb[6];           // RT_SEM_CUDA: the triangles' box (lo xyz, hi xyz), hit_BBox
     const double* sph_rinv;  // 1/radius per sphere (sphere_uvmapping's divide)
     const double* sph_disp;  // per sphere: hsl round trip of its emission (main.c:155-158), 3 doubles

@@ -88,6 +88,9 @@ static_assert(RT_CAND_M * RT_CAND_M * RT_CAND_T1 >= 0x1.8p-89 && RT_CAND_M <= 0x
 #ifndef RT_WAVES_PER_SIMD_Q4
 #define RT_WAVES_PER_SIMD_Q4 RT_WAVES_PER_SIMD_Q
 #endif
+#ifndef RT_WAVES_PER_SIMD_QW        // QB 5 (wide trees): 46 KiB of LDS, three blocks per CU
+#define RT_WAVES_PER_SIMD_QW 3
+#endif
 #ifndef RT_WAVES_PER_SIMD_QS
 #define RT_WAVES_PER_SIMD_QS RT_WAVES_PER_SIMD_Q
 #endif
@@ -328,7 +331,12 @@ static void launch_variant(const KParams& kp_in, void* stream)
     const dim3 g = grid_for(kp_in);
     const hipStream_t st = (hipStream_t)stream;
     KParams kp = kp_in;
-    if (kp.cuda && kp.bvh) hipLaunchKernelGGL((render_kernel_cuda<COUNT, true>), g, dim3(256), 0, st, kp);
+    // a wide tree (rt_bvh.h): the instantiations with uint32 stack entries
+    if (kp.bvh && kp.bvh_wide) {
+        if (kp.cuda) hipLaunchKernelGGL((render_kernel_cuda_w<COUNT>), g, dim3(256), 0, st, kp);
+        else if (kp.sky) hipLaunchKernelGGL((render_kernel_w<COUNT, true>), g, dim3(256), 0, st, kp);
+        else hipLaunchKernelGGL((render_kernel_w<COUNT, false>), g, dim3(256), 0, st, kp);
+    } else if (kp.cuda && kp.bvh) hipLaunchKernelGGL((render_kernel_cuda<COUNT, true>), g, dim3(256), 0, st, kp);
     else if (kp.cuda) hipLaunchKernelGGL((render_kernel_cuda<COUNT, false>), g, dim3(256), 0, st, kp);
     else if (kp.bvh && kp.sky) hipLaunchKernelGGL((render_kernel<COUNT, true, true>), g, dim3(256), 0, st, kp);
     else if (kp.bvh) hipLaunchKernelGGL((render_kernel<COUNT, true, false>), g, dim3(256), 0, st, kp);
@@ -336,7 +344,7 @@ static void launch_variant(const KParams& kp_in, void* stream)
     else hipLaunchKernelGGL((render_kernel<COUNT, false, false>), g, dim3(256), 0, st, kp);
 }
 
-// The 24 render_kernel_q instantiations, (QB, OPQ) x sky x AO, described once:
+// The 28 render_kernel_q instantiations, (QB, OPQ) x sky x AO, described once:
 // with_queue_variant maps the runtime tuple to a QVariant and hands it to f, so
 // the kernel pointer, its name and its occupancy cache cannot disagree.
 template <bool SKY, int AOM, int QB, bool OPQ>
@@ -346,6 +354,7 @@ struct QVariant {
     {
         return QB == 3    ? (OPQ ? "render_kernel_q<QB=3,OP>" : "render_kernel_q<QB=3>")
                : QB == 4  ? "render_kernel_q<QB=4>"
+               : QB == 5  ? "render_kernel_q<QB=5>"
                : QB == -2 ? "render_kernel_q<QB=-2>"
                : QB == -1 ? "render_kernel_q<QB=-1>"
                           : "render_kernel_q<QB=0>";
@@ -365,6 +374,7 @@ static void with_queue_variant(int qb, bool opq, bool sky, bool ao, F&& f)
     if (qb == 3 && opq) with_queue_variant_qb<3, true>(sky, ao, f);
     else if (qb == 3) with_queue_variant_qb<3, false>(sky, ao, f);
     else if (qb == 4) with_queue_variant_qb<4, false>(sky, ao, f);
+    else if (qb == 5) with_queue_variant_qb<5, false>(sky, ao, f);
     else if (qb == -2) with_queue_variant_qb<-2, false>(sky, ao, f);
     else if (qb < 0) with_queue_variant_qb<-1, false>(sky, ao, f);
     else with_queue_variant_qb<0, false>(sky, ao, f);
@@ -411,6 +421,11 @@ const char* last_render_kernel() { return t_last_kernel; }
 // pack_bvh_h refused (a coordinate beyond binary16's range, a leaf index above
 // 65535, an oversized leaf) renders with QB 4's walk when its stack fits there,
 // else with the fixed-grid kernel; a shallow one keeps the queue kernel.
+// A wide tree (kp.bvh_wide, rt_bvh.h: indices beyond 16 bits) takes QB 5 --
+// the deep-tree walk over its own 64-byte nodes kp.bvhw with a 24-bit stack --
+// when those nodes packed and its stack bound is at most kStackQW, else the
+// fixed grid's wide instantiation (uint32 stack, kStack4 entries); no narrow
+// kernel ever walks it, and a narrow tree never takes a wide kernel.
 RenderChoice choose_render(const KParams& kp, bool task_ok)
 {
     RenderChoice c;
@@ -418,6 +433,14 @@ RenderChoice choose_render(const KParams& kp, bool task_ok)
     c.qb = 0;
     c.opq = false;
     c.stack_cap = kp.bvh ? kStack4 : 0;
+    if (kp.bvh != nullptr && kp.bvh_wide) {
+        if (task_ok && kp.chunks > 1 && !kp.cuda && !kp.sums && kp.bvhw != nullptr && kp.bvh_stack <= kStackQW) {
+            c.queue = true;
+            c.qb = 5;
+            c.stack_cap = kStackQW;
+        }
+        return c;
+    }
     bool qbvh = false;
     if (kp.bvh != nullptr && kp.bvh_stack <= kStackQN) {
         c.qb = kp.bvh_steps <= 3 || kp.bvh_stack > kStackQ4 ? 3 : 4;
@@ -477,7 +500,9 @@ int launch_render(const KParams& kp, void* stream)
         }
     } else {
         launch_variant<false>(kp, stream);
-        t_last_kernel = kp.cuda ? "render_kernel_cuda" : kp.bvh ? "render_kernel<BVH>" : "render_kernel";
+        t_last_kernel = kp.cuda ? "render_kernel_cuda"
+                        : kp.bvh ? (kp.bvh_wide ? "render_kernel<BVH32>" : "render_kernel<BVH>")
+                                 : "render_kernel";
     }
     if (kp.chunks > 1) {
         const long long npx = (long long)kp.band_rows * kp.W;

@@ -387,12 +387,20 @@ __device__ __forceinline__ void decode_task(KParamsK K, unsigned t, uint32_t e[k
     e[4] = (uint32_t)chunk_start(K->S, K->chunks, K->chunk_taper, K->chunk_den, K->qm_chunks, chunk + 1u);
 }
 
+// QB 5: a wide tree (rt_bvh.h BvhBuild::wide) -- the non-opaque deep-tree
+// kernel (QB 3, not OPQ: every material branch, the adaptive visit count, the
+// far-origin margins, the walk priority) over the BvhNodeW nodes kp.bvhw with
+// the 24-bit stack bvh_stack_qw (kStackQW entries); its 46 KiB of LDS allow
+// three blocks per CU, RT_WAVES_PER_SIMD_QW waves per SIMD.
 template <bool SKY, int AOM, int QB, bool OPQ = false>   // OPQ: (BVH scenes) every material opaque
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QB < 0 ? RT_WAVES_PER_SIMD_QS
                                                                      : QB == 4 ? RT_WAVES_PER_SIMD_Q4
+                                                                     : QB == 5 ? RT_WAVES_PER_SIMD_QW
                                                                                : RT_WAVES_PER_SIMD_Q)))
 void render_kernel_q(const KParams kp)
 {
+    static_assert(QB != 5 || !OPQ, "the wide-tree kernel has no opaque specialisation");
+    constexpr bool DEEP = QB == 3 || QB == 5;            // the deep-tree walk (64-byte nodes in HBM)
     // incomingLight / rayColor in LDS: both for the non-BVH kernels, incomingLight
     // alone for the opaque deep-tree kernel (its stack leaves room for 3 doubles)
     constexpr int QIR = QB <= 0 ? 2 : (QB == 3 && OPQ) ? 1 : 0;
@@ -418,7 +426,7 @@ void render_kernel_q(const KParams kp)
     bool owns = false;               // the lane's LDS sums belong to task (chunk, p)
     // every instantiation but the deep-tree one (QB 3, where the table's
     // registers cost spills): each wave decodes its batches of tasks into LDS
-    constexpr bool TTAB = QB != 3;
+    constexpr bool TTAB = !DEEP;
     __shared__ uint32_t ttab_lds[TTAB ? 4 * kTaskWords * 64 : 1];
     unsigned qidx = 0;               // (TTAB) partial index of the lane's task
     Stream st;                       // draw stream of the sample in flight (next31 for refraction / AO)
@@ -426,7 +434,7 @@ void render_kernel_q(const KParams kp)
     // shallow trees (QB 4: depth4 <= 4, e.g. the 50-node sweep tree) keep
     // their top nodes in LDS, as 128-byte nodes; deep trees (QB 3) walk the
     // 64-byte nodes in HBM (HN; host: kp.bvhh set)
-    constexpr bool HN = QB == 3;
+    constexpr int HN = QB == 5 ? 2 : QB == 3 ? 1 : 0;    // bvh_step's node form
     constexpr int NTOP = QB == 4 ? RT_QB_TOP : 0;
     if (NTOP > 0) {                          // the tree's top nodes into LDS, once per block
         float4* dst = (float4*)bvh_top_q<NTOP>();
@@ -473,15 +481,15 @@ void render_kernel_q(const KParams kp)
                 __builtin_amdgcn_s_setprio(RT_WALK_PRIO);
 #endif
                 const V3 dd = L.cast_dir();
-                const Ray32 r32 = ray32<QB == 3 && !OPQ>(kp, L.o, dd);
-                unsigned short* stk = bvh_stack_q<QB, OPQ>();
+                const Ray32 r32 = ray32<DEEP && !OPQ>(kp, L.o, dd);
+                const auto stk = bvh_stack_for_q<QB, OPQ>();
                 const BvhNode4* top = NTOP > 0 ? bvh_top_q<NTOP>() : nullptr;
                 // deep trees (QB 3): at least RT_QW_MIN visits, then more while at
                 // least RT_QW_LANES lanes of the wave are still walking, up to
                 // RT_QW_MAX (long walks -- e.g. rays skimming RTX_MAP/nature's
                 // terrain -- finish in fewer rounds, short ones hand the wave back
                 // to the path work as before)
-                constexpr int JMIN = QB == 3 ? RT_QW_MIN : QB, JMAX = QB == 3 ? RT_QW_MAX : QB;
+                constexpr int JMIN = DEEP ? RT_QW_MIN : QB, JMAX = DEEP ? RT_QW_MAX : QB;
 #pragma unroll 1
                 for (int j = 0; j < JMAX; ++j) {
                     if (L.state == SM_TRAV) {

@@ -388,6 +388,7 @@ int prepare_scene(const rt_scene* scene, HostScene& hs, std::string& err)
     f.bvh_nodes = (int)bvh.nodes4.size();
     f.bvh_depth = bvh.depth4;
     f.bvh_stack4 = bvh.stack4;
+    f.bvh_wide = bvh.wide;
     f.s_rel = bvh.s_rel;
     f.s_abs = bvh.s_abs;
     f.r_scene = bvh.r_scene;
@@ -400,10 +401,14 @@ int prepare_scene(const rt_scene* scene, HostScene& hs, std::string& err)
                     for (int a = 0; a < 3; ++a) rb = std::max({rb, std::fabs(nd.lo[a][c]), std::fabs(nd.hi[a][c])});
         f.bvh_rbox = std::isfinite(rb) ? rb * (1.0f + 0x1p-20f) : HUGE_VALF;
         float rbh = 0.0f;
-        if (!bvh.nodes4.empty() && pack_bvh_h(bvh.nodes4, hs.bvhh, rbh))
+        if (!bvh.nodes4.empty() && !bvh.wide && pack_bvh_h(bvh.nodes4, hs.bvhh, rbh))
             f.bvh_rbox = std::max(f.bvh_rbox, rbh * (1.0f + 0x1p-20f));   // one bound serves both forms
         else
             hs.bvhh.clear();
+        if (bvh.wide && pack_bvh_w(bvh.nodes4, hs.bvhw, rbh))            // (a wide tree: its own 64-byte form)
+            f.bvh_rbox = std::max(f.bvh_rbox, rbh * (1.0f + 0x1p-20f));
+        else
+            hs.bvhw.clear();
     }
     hs.bvh.swap(bvh.nodes4);
     hs.tri_orig.swap(bvh.order);

@@ -23,6 +23,7 @@ struct SceneFacts {
     double cbb[6] = {0, 0, 0, 0, 0, 0};   // triangles' box (RT_SEM_CUDA hit_BBox)
     int sky_w = 0, sky_h = 0;
     int bvh_nodes = 0, bvh_depth = 0, bvh_stack4 = 0;
+    bool bvh_wide = false;           // BvhBuild::wide: indices beyond 16 bits (32-bit stacks, BvhNodeW, no BvhNodeH)
     double s_rel = 0.0, s_abs = 0.0, r_scene = 0.0, k_delta = 0.0;
     double sph_bound = 0.0;          // max over spheres of max_a |c_a| + |r| (+inf for an infinite one); a NaN
                                      // term (a NaN centre coordinate or radius) is dropped, unlike in coord_max
@@ -50,6 +51,7 @@ struct SceneArrays {
     Array<DevMat> texels;
     Array<BvhNode4> bvh;             // 4-wide BVH; empty: no BVH (few triangles)
     Array<BvhNodeH> bvhh;            // the same tree in 64-byte nodes, or empty (does not fit binary16)
+    Array<BvhNodeW> bvhw;            // a wide tree (facts.bvh_wide) in its 64-byte nodes, or empty (does not pack)
     Array<int> tri_orig;             // leaf order -> caller's triangle index
     Array<DevMat> sky;               // sky texels (scene->sky_mat_list), or empty
     Array<double> sph_rinv;          // 1/radius per sphere

@@ -260,7 +260,7 @@ __device__ __forceinline__ double ao_tail(bool hit, const V3 p, const V3 dir, do
 }
 
 // ambient_occlusion, main.c:94-116: one cast, only distance/dst matters.
-template <bool COUNT, bool BVH, bool CU = false>
+template <bool COUNT, bool BVH, bool CU = false, class SE = unsigned short>
 __device__ __forceinline__ double ao_factor(const KParams& kp, const V3 p, const V3 n, double AO, Stream& st,
                                             Cnt& cnt)
 {
@@ -268,7 +268,7 @@ __device__ __forceinline__ double ao_factor(const KParams& kp, const V3 p, const
     const V3 dir = normalize(n + rd);
     double t;
     int idx;
-    const int kind = closest_hit<COUNT, BVH, CU>(kp, p, dir, t, idx, cnt);
+    const int kind = closest_hit<COUNT, BVH, CU, false, SE>(kp, p, dir, t, idx, cnt);
     return ao_tail(kind != HIT_NONE, p, dir, t, AO);
 }
 

@@ -10,7 +10,7 @@ namespace rt {
 // the caller's order (BVH leaf order), an equal dst replaces a triangle
 // winner with a larger caller index (orig).  det >= 1e-6 >= 2^-400 puts
 // 1/det on the exact fast division (div_core).
-// O32 (BVH leaves: a tree holds < 65535 nodes, so k * sizeof(TriGeo) < 2^32):
+// O32 (BVH leaves: a tree holds at most 2^24 triangles, so k * sizeof(TriGeo) < 2^32):
 // the records are read at 32-bit byte offsets from the array's scalar base.
 // UNI (the brute-force scan, k wave-uniform): the record through the scalar
 // unit (s_load into SGPRs, read by the VALU as scalar operands), no vector
@@ -107,7 +107,7 @@ __device__ __forceinline__ void tri_test_bf(const KParams& kp, int k, const V3 o
 // boxes (float storage rounded outward; the slab math runs in double); leaf
 // children are tested on the spot, the nearest hit internal child is entered
 // next and the others are pushed on a per-lane LDS stack (uint16
-// [kStack4][256], conflict-free).  A box is skipped only when no triangle in
+// [kStack4][256], conflict-free; uint32 for a wide tree, rt_bvh.h).  A box is skipped only when no triangle in
 // it can win or tie (rt_bvh.cpp): the ray misses the padded box, leaves it
 // behind the origin (tmax < -sabs), or enters it beyond best*(1+srel)+sabs.
 // Slab reciprocals use |d_i| >= 2^-200, which keeps the products finite
@@ -135,6 +135,56 @@ __device__ __forceinline__ unsigned short* bvh_stack_q()
 {
     __shared__ unsigned short stkq_lds[(QB == 4 ? kStackQ4 : OPQ ? kStackQ : kStackQN) * 256];
     return stkq_lds + threadIdx.x;
+}
+// Stack access by element type: a column of uint16 (narrow trees) or uint32
+// (wide trees on the fixed grid) entries, 256 lanes apart.
+template <class T>
+__device__ __forceinline__ void stk_put(T* stk, int sp, int v) { stk[sp * 256] = (T)v; }
+template <class T>
+__device__ __forceinline__ int stk_get(const T* stk, int sp) { return (int)stk[sp * 256]; }
+// Wide trees (rt_bvh.h BvhBuild::wide; node indices < 2^24) on the fixed grid:
+// uint32 [kStack4][256], 48 KiB with the 22 KiB of sums and draws, two blocks per CU.
+__device__ __forceinline__ uint32_t* bvh_stack32()
+{
+    __shared__ uint32_t stk32_lds[kStack4 * 256];
+    return stk32_lds + threadIdx.x;
+}
+template <class SE>
+__device__ __forceinline__ SE* bvh_stack_of()
+{
+    if constexpr (sizeof(SE) == 4) return bvh_stack32();
+    else return bvh_stack();
+}
+// ... in the queue kernel (QB 5): kStackQW = 32 entries of 24 bits, split into a
+// uint16 column and a uint8 column, 24 KiB: with the 22 KiB of sums and draws
+// 46 KiB per block, three blocks (12 waves) per CU.  (32 uint32 entries would
+// make it 54 KiB: two blocks.)
+constexpr int kStackQW = 32;
+struct Stack24 {
+    unsigned short* lo;
+    unsigned char* hi;
+};
+__device__ __forceinline__ Stack24 bvh_stack_qw()
+{
+    __shared__ unsigned short stkw_lo_lds[kStackQW * 256];
+    __shared__ unsigned char stkw_hi_lds[kStackQW * 256];
+    return Stack24{stkw_lo_lds + threadIdx.x, stkw_hi_lds + threadIdx.x};
+}
+__device__ __forceinline__ void stk_put(Stack24 stk, int sp, int v)
+{
+    stk.lo[sp * 256] = (unsigned short)((unsigned)v & 0xffffu);
+    stk.hi[sp * 256] = (unsigned char)((unsigned)v >> 16);
+}
+__device__ __forceinline__ int stk_get(Stack24 stk, int sp)
+{
+    return (int)((unsigned)stk.lo[sp * 256] | ((unsigned)stk.hi[sp * 256] << 16));
+}
+// the stack of a queue-kernel instantiation
+template <int QB, bool OPQ>
+__device__ __forceinline__ auto bvh_stack_for_q()
+{
+    if constexpr (QB == 5) return bvh_stack_qw();
+    else return bvh_stack_q<QB, OPQ>();
 }
 // ... and the QB 4 block's copy of the tree's top nodes (RT_QB_TOP x 128 B)
 template <int N>
@@ -276,6 +326,11 @@ __device__ __forceinline__ void box4(const KParams& kp, const BvhNode4* nd, cons
 // with rbox >= |org| + |rel| (host) the total stays below E / 3.
 __device__ __forceinline__ float h16lo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
 __device__ __forceinline__ float h16hi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+// WIDE: the node is a BvhNodeW (rt_bvh.h) read from kp.bvhw: the same planes,
+// origin and counts, and the children from the two 32-bit bases -- internal
+// child c is node_base + (internal slots before c), leaf child c starts at
+// tri_base + (counts of the leaf slots before c).
+template <bool WIDE = false>
 __device__ __forceinline__ void box4h(const KParams& kp, const BvhNodeH* nd, uint32_t nb, const Ray32& r, float cull,
                                       bool h[4], float tn[4], int Ch[4], int Cn[4])
 {
@@ -285,7 +340,8 @@ __device__ __forceinline__ void box4h(const KParams& kp, const BvhNodeH* nd, uin
     uint2 px, py, pz, qx, qy, qz;
     uint4 t;
     {                                                    // the whole node in four 16-byte loads (HBM at
-        const uint4* q = nd ? (const uint4*)nd                         // 32-bit offsets, or the LDS copy),
+        const uint4* q = WIDE ? (const uint4*)((const char*)kp.bvhw + nb)
+                         : nd ? (const uint4*)nd                       // 32-bit offsets, or the LDS copy),
                             : (const uint4*)((const char*)kp.bvhh + nb);   // rows selected by sign
         const uint4 r0 = q[0], r1 = q[1], r2 = q[2];
         t = q[3];
@@ -298,7 +354,18 @@ __device__ __forceinline__ void box4h(const KParams& kp, const BvhNodeH* nd, uin
     const float Ax = fmaf(h16lo(t.x), r.ix, r.ax), Ay = fmaf(h16hi(t.x), r.iy, r.ay), Az = fmaf(h16lo(t.y), r.iz, r.az);
     const float Bx = fmaf(h16lo(t.x), r.ix, r.bx), By = fmaf(h16hi(t.x), r.iy, r.by), Bz = fmaf(h16lo(t.y), r.iz, r.bz);
     const uint32_t cn = t.y >> 16;
-    Ch[0] = (int)(t.z & 0xffffu); Ch[1] = (int)(t.z >> 16); Ch[2] = (int)(t.w & 0xffffu); Ch[3] = (int)(t.w >> 16);
+    if constexpr (WIDE) {
+        uint32_t nn = t.z, kk = t.w;                     // next internal child, next leaf's first triangle
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint32_t nib = (cn >> (4 * c)) & 15u;
+            Ch[c] = (int)(nib == 0u ? nn : kk);
+            nn += nib == 0u ? 1u : 0u;
+            kk += nib == 15u || nib == 0u ? 0u : nib;
+        }
+    } else {
+        Ch[0] = (int)(t.z & 0xffffu); Ch[1] = (int)(t.z >> 16); Ch[2] = (int)(t.w & 0xffffu); Ch[3] = (int)(t.w >> 16);
+    }
     const float Px[4] = {h16lo(px.x), h16hi(px.x), h16lo(px.y), h16hi(px.y)};
     const float Py[4] = {h16lo(py.x), h16hi(py.x), h16lo(py.y), h16hi(py.y)};
     const float Pz[4] = {h16lo(pz.x), h16hi(pz.x), h16lo(pz.y), h16hi(pz.y)};
@@ -332,9 +399,11 @@ __device__ __forceinline__ unsigned* diag_cnt()
     __shared__ unsigned dc_lds[RT_DIAG_STALE == 2 ? 2 * 256 : 1];
     return dc_lds + threadIdx.x;
 }
-template <bool COUNT, bool CU, int NTOP = 0, bool H = false>
+// H: 0 the 128-byte nodes, 1 BvhNodeH, 2 BvhNodeW; STK: the lane's stack (a
+// uint16 or uint32 column, or the QB 5 kernel's Stack24; stk_put / stk_get)
+template <bool COUNT, bool CU, int NTOP = 0, int H = 0, class STK>
 __device__ __forceinline__ bool bvh_step(const KParams& kp, const V3 o, const V3 d, const Ray32& r32,
-                                         unsigned short* stk, int& node, int& sp, double& best, int& kind,
+                                         STK stk, int& node, int& sp, double& best, int& kind,
                                          int& win, int& win_orig, Cnt& cnt, const void* top = nullptr)
 {
     if constexpr (RT_DIAG_STALE && (COUNT || RT_DIAG_STALE == 2)) {
@@ -358,7 +427,9 @@ __device__ __forceinline__ bool bvh_step(const KParams& kp, const V3 o, const V3
     float tn[4];
     int Ch[4], Cn[4];
     const bool in_top = NTOP > 0 && node < NTOP;
-    if (H)
+    if (H == 2)
+        box4h<true>(kp, nullptr, (uint32_t)node * (uint32_t)sizeof(BvhNodeW), r32, cull32(kp, best), h, tn, Ch, Cn);
+    else if (H)
         box4h(kp, in_top ? (const BvhNodeH*)top + node : nullptr, (uint32_t)node * (uint32_t)sizeof(BvhNodeH), r32,
               cull32(kp, best), h, tn, Ch, Cn);
     else
@@ -388,7 +459,7 @@ __device__ __forceinline__ bool bvh_step(const KParams& kp, const V3 o, const V3
             if (!RT_DIAG_STALE && COUNT && sp >= kp.stack_cap) cnt.c[RT_CNT_BVH_STACK_OVER] += 1;
             if (!COUNT || sp < kStack4) {    // COUNT walks use the fixed grid's stack
                 if (RT_DIAG_STALE && (COUNT || RT_DIAG_STALE == 2) && sp < 16) diag_lds()[sp * 256] = tpush;
-                stk[sp * 256] = (unsigned short)push;
+                stk_put(stk, sp, push);
                 ++sp;
             }
             (void)tpush;
@@ -417,17 +488,17 @@ __device__ __forceinline__ bool bvh_step(const KParams& kp, const V3 o, const V3
     }
     if (sp == 0) return false;
     --sp;
-    node = stk[sp * 256];
+    node = stk_get(stk, sp);
     if (RT_DIAG_STALE && (COUNT || RT_DIAG_STALE == 2))
         diag_lds()[16 * 256] = sp < 16 ? diag_lds()[sp * 256] : -__builtin_huge_valf();
     return true;
 }
 
-template <bool COUNT, bool CU>
+template <bool COUNT, bool CU, class SE = unsigned short>
 __device__ __forceinline__ void tris_bvh(const KParams& kp, const V3 o, const V3 d, double& best, int& kind,
                                          int& win, int& win_orig, Cnt& cnt)
 {
-    unsigned short* stk = bvh_stack();
+    SE* stk = bvh_stack_of<SE>();
     const Ray32 r32 = ray32(kp, o, d);
     int node = 0, sp = 0;
     while (bvh_step<COUNT, CU>(kp, o, d, r32, stk, node, sp, best, kind, win, win_orig, cnt)) {
@@ -468,7 +539,8 @@ __device__ __forceinline__ int cast_spheres(const KParams& kp, const V3 o, const
     return win;
 }
 
-template <bool COUNT, bool BVH, bool CU = false, bool AMGM = false>
+// SE: the BVH stack's element type (uint32_t for a wide tree, rt_bvh.h)
+template <bool COUNT, bool BVH, bool CU = false, bool AMGM = false, class SE = unsigned short>
 __device__ __forceinline__ int closest_hit(const KParams& kp, const V3 o, const V3 d, double& t_best, int& idx,
                                            Cnt& cnt)
 {
@@ -480,7 +552,7 @@ __device__ __forceinline__ int closest_hit(const KParams& kp, const V3 o, const 
     if (CU && kp.nt > 0 && !cuda_bbox(kp, o, d)) {
         // main_cuda.cu:40-45: the ray misses the mesh box, no triangle tested
     } else if (BVH) {
-        tris_bvh<COUNT, CU>(kp, o, d, best, kind, win, win_orig, cnt);
+        tris_bvh<COUNT, CU, SE>(kp, o, d, best, kind, win, win_orig, cnt);
     } else if (!COUNT && !kp.tri_orig) {
         for (int k = 0; k < kp.nt; ++k) tri_test_bf<CU>(kp, k, o, d, best, kind, win);
     } else {

@@ -191,6 +191,72 @@ def with_cuda_materials(mesh):
     return mesh
 
 
+# The README box's floor as heightfield_mesh's `box`: (x0, x1, y0, z0, z1), the
+# ground y0 just above the floor sphere's top (y = -1).
+README_FLOOR = (-1.0, 1.0, -0.999, -4.0, 0.4)
+
+
+def heightfield_mesh(n, seed, amp, box, nm=1, alpha=None):
+    """A terrain of 2 n^2 triangles (the scale of a Mineways map export): an
+    (n + 1)^2 grid over box = (x0, x1, y0, z0, z1), every inner vertex jittered
+    by up to 0.3 of a cell in x and z; heights within [y0, y0 + amp]: rolling
+    hills (four sines with seeded phases) plus a per-vertex roughness of a few
+    cells' width; each cell is split along alternating diagonals and every
+    triangle faces up.  nm
+    materials (triangle (i, j) takes (i + j) % nm) of one 2x2 texel table
+    each: two opaque colours on the diagonal, and off it a third colour whose
+    alpha is `alpha` (refraction; 1.0 when None) and, when alpha is given, an
+    alpha-0 hole.  uvs are the vertices' grid fractions, so every texel shows.
+    Filled through a numpy view of the ctypes array.  Returns (triangles,
+    quelMatPourTri, mat_list, tw, th, n_materials); deterministic in seed."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    x0, x1, y0, z0, z1 = box
+    g = np.arange(n + 1) / n
+    jx, jz = rng.uniform(-0.3, 0.3, (2, n + 1, n + 1)) / n
+    jx[[0, -1], :] = jx[:, [0, -1]] = jz[[0, -1], :] = jz[:, [0, -1]] = 0.0
+    fx, fz = g[:, None] + jx, g[None, :] + jz            # [i, j]: i along x, j along z
+    ph = rng.uniform(0.0, 2.0 * np.pi, 4)
+    tau = 2.0 * np.pi
+    hills = (0.45 + 0.2 * np.sin(2 * tau * fx + ph[0]) * np.cos(3 * tau * fz + ph[1]) + 0.15 * np.sin(5 * tau * fz + ph[2])
+             + 0.1 * np.sin(7 * tau * fx + ph[3]))
+    h = np.clip(hills + rng.uniform(0.0, 4.0 / n, (n + 1, n + 1)), 0.0, 1.0)
+    P = np.stack([x0 + (x1 - x0) * fx, y0 + amp * h, z0 + (z1 - z0) * fz], axis=-1)
+    T = np.stack([np.broadcast_to(g[:, None], fx.shape), np.broadcast_to(g[None, :], fz.shape)], axis=-1)
+    # the cell's corners; N = (B - A) x (C - A) points up for A, A + z, A + x
+    c00, c10, c01, c11 = (slice(0, n), slice(0, n)), (slice(1, n + 1), slice(0, n)), \
+                         (slice(0, n), slice(1, n + 1)), (slice(1, n + 1), slice(1, n + 1))
+    even = ((np.arange(n)[:, None] + np.arange(n)[None, :]) % 2 == 0)[..., None]
+
+    def corners(V):
+        a, b, c, d = V[c00], V[c10], V[c01], V[c11]
+        # even cells: (00, 01, 10), (10, 01, 11); odd cells: (00, 01, 11), (00, 11, 10)
+        t0 = (a, c, np.where(even, b, d))
+        t1 = (np.where(even, b, a), np.where(even, c, d), np.where(even, d, b))
+        return [np.stack([t0[k], t1[k]], axis=2).reshape(2 * n * n, -1) for k in range(3)]
+
+    nt = 2 * n * n
+    tris = (Triangle * nt)()
+    rows = np.frombuffer(tris, dtype=np.float64).reshape(nt, C.sizeof(Triangle) // 8)
+    A, B, Cv = corners(P)
+    uA, uB, uC = corners(T)
+    rows[:, 0:3], rows[:, 3:6], rows[:, 6:9] = A, B, Cv
+    m = material(SKY, BLACK, 0.0, 0.0, 0.0, 0.0)          # mesh.h:206
+    rows[:, 9:19] = np.frombuffer(m, dtype=np.float64)
+    rows[:, 19:21], rows[:, 21:23], rows[:, 23:25] = uA, uB, uC
+    ij = np.arange(n)[:, None] + np.arange(n)[None, :]
+    qm = (C.c_int * nt)()
+    np.frombuffer(qm, dtype=np.int32)[:] = np.repeat((ij % nm).reshape(-1), 2)
+    mats = (Material * (4 * nm))()
+    for k in range(nm):
+        c0, c1, c2 = (tuple(rng.uniform(0.2, 0.9, 3)) for _ in range(3))
+        mats[4 * k + 0] = material(c0, BLACK, 0.0, 0.0, 1.0, 0.0)
+        mats[4 * k + 1] = material(c2, BLACK, 0.0, 0.0, 1.0 if alpha is None else alpha, 1.3)
+        mats[4 * k + 2] = material(c2, BLACK, 0.0, 0.0, 1.0 if alpha is None else 0.0, 0.0)
+        mats[4 * k + 3] = material(c1, BLACK, 0.0, 0.3, 1.0, 0.0)
+    return tris, qm, mats, 2, 2, nm
+
+
 def synthetic_cornell(n_spheres=10, n_tris=0, seed=7):
     """SURVEY.md §8(d)'s roofline-sweep scenes: the README box with
     n_spheres - 10 extra small spheres (70 % diffuse, 15 % mirror, 15 %

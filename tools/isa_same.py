@@ -2,7 +2,7 @@
 """Compare the device code of two builds kernel by kernel.
 
     make -C tipe-raytracer_amd asm          # at each commit: rt_kernels.s
-    tools/isa_same.py OLD.s NEW.s [--allow-reordered]
+    tools/isa_same.py OLD.s NEW.s [--allow-reordered] [--allow-new]
 
 Comments are stripped and the function-index part of local labels
 (.LBB<n>_, .Lfunc_end<n>, .Ltmp<n>) is normalised; kernels are matched by
@@ -14,6 +14,9 @@ must be identical: exit status 0.
 instruction): a kernel may differ when its descriptor block, its instruction
 count and its multiset of opcode mnemonics are all identical.  Those kernels
 are listed with their differing lines; anything beyond that class fails.
+
+--allow-new (a change that adds kernels): symbols present only in NEW.s are
+listed as new and do not fail; a symbol missing from NEW.s still does.
 """
 import collections
 import difflib
@@ -66,16 +69,18 @@ def insns(lines):
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     allow = "--allow-reordered" in sys.argv[1:]
+    allow_new = "--allow-new" in sys.argv[1:]
     if len(args) != 2:
         sys.exit(__doc__)
     old, new = kernels(args[0]), kernels(args[1])
     bad = 0
-    if set(old) != set(new):
+    gone, added = sorted(set(old) - set(new)), sorted(set(new) - set(old))
+    if gone or (added and not allow_new):
         bad += 1
-        for k in sorted(set(old) - set(new)):
-            print("only in %s: %s" % (args[0], k))
-        for k in sorted(set(new) - set(old)):
-            print("only in %s: %s" % (args[1], k))
+    for k in gone:
+        print("only in %s: %s" % (args[0], k))
+    for k in added:
+        print("%s %s: %s" % ("NEW in" if allow_new else "only in", args[1], k))
     same, reordered = 0, []
     for k in sorted(set(old) & set(new)):
         (b0, d0), (b1, d1) = old[k], new[k]
