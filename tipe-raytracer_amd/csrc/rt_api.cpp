@@ -199,6 +199,7 @@ void make_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling
     kp.cand_orig = sc->cand_orig;
     kp.sph_slot = sc->sph_slot;
     kp.ns_merge = f.ns_merge;
+    kp.ns_fwd = f.ns_fwd;
     kp.nt = f.nt;
     kp.tw = f.tw;
     kp.th = f.th;
@@ -449,6 +450,7 @@ int rt_scene_upload(int device, const rt_scene* scene, rt_device_scene** out)
     HostScene hs;
     std::string err;
     if ((rc = prepare_scene(scene, hs, err))) return fail(rc, "%s", err.c_str());
+    pair_forward(scene, hs);
     rt_device_scene* ds = new rt_device_scene();
     ds->device = device;
     ds->facts = hs.facts;

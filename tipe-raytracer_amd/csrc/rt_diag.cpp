@@ -72,6 +72,7 @@ int rt_verify_sphere_pass(const rt_scene* scene, const double* rays, long long n
     kp.cand_orig = ds->cand_orig;
     kp.sph_slot = ds->sph_slot;
     kp.ns_merge = ds->facts.ns_merge;
+    kp.ns_fwd = ds->facts.ns_fwd;
     DevArray<double> d_rays;
     hipError_t e = d_rays.upload(rays, (size_t)n * 6);
     if (e == hipSuccess) e = run_counted(counts, [&](u64* d) { return launch_verify_spheres(kp, d_rays, n, d); });

@@ -168,6 +168,8 @@ struct KParams {
     int bvh_far;             // some ray origin may lie beyond R_b: a sphere or the camera does
     int ns_merge;            // the first ns_merge (even) candidate records are pairs that may share one
                              // root tail (rt_scene_prep.cpp order_candidates; a hint, any value gives the same result)
+    int ns_fwd;              // the next ns_fwd (even) records are forward pairs, which share it by another test (pair_forward)
+                             // (a hint as well; in the padding before cand_orig: no field moves)
     const int* cand_orig;    // [ns_pad] candidate record (slot) j describes sphere cand_orig[j] of sph
     const SphGeo* sph_slot;  // [ns_pad] sph[cand_orig[j]]: the candidate pass's winner retest
 };

@@ -73,6 +73,10 @@
 #endif
 static_assert(RT_CAND_M * RT_CAND_M * RT_CAND_T1 >= 0x1.8p-89 && RT_CAND_M <= 0x1p-20,
               "candidate half-width M must be >= 8 x the sqrt error bound 2^-47.2/sqrt(T1)");
+// Forward pairs' liveness certificate (spheres_closest): a sphere is dead for a
+// lane with h > 2^-RT_FWD_HEXP Hs and ca > -2^-RT_FWD_CEXP Hs^2.
+#define RT_FWD_HEXP 16
+#define RT_FWD_CEXP 44
 // Occupancy bounds (waves per SIMD): the fixed-grid kernels, the fixed-grid
 // BVH variant (traversal state + LDS stack), and the queue kernel with its
 // shallow-tree (QB 4) and sphere-only (QB < 0) instantiations.
@@ -128,7 +132,8 @@ static_assert(RT_CAND_M * RT_CAND_M * RT_CAND_T1 >= 0x1.8p-89 && RT_CAND_M <= 0x
 #endif                              // slot; stack entries below depth 16 only)
 #ifndef RT_DIAG_MERGE               // tools/merge_share.py: render_kernel_q's RT_QUEUE_TRACE record carries the
 #define RT_DIAG_MERGE 0             // wave's flagged sphere pairs that ran one root tail / two (spheres_closest)
-#endif                              // in place of rounds and tasks
+#endif                              // in place of rounds and tasks, and the same of its forward pairs in
+                                    // place of the two clocks
 
 // The device code by concern, in definition order (one translation unit).
 #include "rt_vec.h"

@@ -173,10 +173,12 @@ int order_candidates(const rt_scene* scene, int ns_pad, bool finite, std::vector
     auto rad = [&](int i) { return std::fabs(scene->sphere_list[i].radius); };
     std::vector<char> used((size_t)ns, 0);
     // RT_CAND_MERGE (tests, A/B runs): "off" flags no pair, "all" flags every
-    // pair, both in the caller's order -- the results must not notice
+    // pair ("fwd-all": none here, every pair a forward pair in pair_forward),
+    // all in the caller's order -- the results must not notice
     const char* mode = std::getenv("RT_CAND_MERGE");
     const bool all = mode && !std::strcmp(mode, "all"), off = mode && !std::strcmp(mode, "off");
-    if (all || off) {
+    const bool fwd_all = mode && !std::strcmp(mode, "fwd-all");
+    if (all || off || fwd_all) {
         for (int i = 0; i < ns_pad; ++i) order.push_back(i);
         return all ? ns_pad : 0;
     }
@@ -413,6 +415,114 @@ int prepare_scene(const rt_scene* scene, HostScene& hs, std::string& err)
     hs.bvh.swap(bvh.nodes4);
     hs.tri_orig.swap(bvh.order);
     return RT_OK;
+}
+
+// Forward pairs: the ns_fwd candidate records after the flagged ones
+// (rt_spheres.h spheres_closest; KParams::ns_fwd).  A step of its own after
+// prepare_scene, which keeps the order its rule gives (tests/test_scene_prep.py):
+// it moves the chosen pairs to the front of the unflagged records, in
+// cand_orig, sph_cand and sph_slot alike; the rest keep their order.  Like the
+// flags of order_candidates a performance hint only.
+// The kernel merges such a pair's tails when no lane moves
+// towards both spheres, (o - C) . d < 0 for both, and a ray does that only
+// when its direction lies in the wedge between the two half-spaces whose
+// normals point from its origin to the two centres.  The wedge is thin when
+// the origin lies between the spheres: outside both, with the centres nearly
+// opposite.  The centroid P of all other spheres' centres stands for where rays
+// start (every ray but the camera's starts on a sphere).  Among the kMergeScan
+// unflagged spheres of largest radius (large spheres are the ones whose
+// D > 0 on most rays, which order_candidates' rule cannot merge), in descending
+// radius, each takes the unpaired partner with the smallest c = cos of the
+// angle C_i P C_j, among partners that are disjoint from it by a margin, d^2 >
+// (R_i + R_j)^2 (1 + 2^-12) (touching, overlapping and nested spheres have an
+// origin on or in one of them where a ray moves towards both in half of the
+// directions), with P outside both, and the pair is flagged when c <= -0.9.
+// P is a coarse stand-in, so the threshold is loose: the README box's left/right
+// and floor/ceiling walls give c = -0.9675 (its back wall drags P 64 units
+// behind the box), while two walls that meet in an edge give c near 0 and a
+// wall with a small sphere in front of it c > 0.9; a wrongly flagged pair
+// costs its test, never the result.  A non-finite sphere: no pair.
+// RT_CAND_MERGE: "all" and "off" leave no forward pair, "fwd-all" makes every
+// pair of the caller's order one.
+void pair_forward(const rt_scene* scene, HostScene& hs)
+{
+    constexpr double kFwdCos = -0.9;
+    SceneFacts& f = hs.facts;
+    const int ns = f.ns;
+    f.ns_fwd = 0;
+    const char* mode = std::getenv("RT_CAND_MERGE");
+    if (mode && (!std::strcmp(mode, "all") || !std::strcmp(mode, "off"))) return;
+    if (mode && !std::strcmp(mode, "fwd-all")) {
+        f.ns_fwd = f.ns_pad - f.ns_merge;        // (order_candidates flagged none: all of them)
+        return;
+    }
+    if (ns < 3 || !std::isfinite(f.cand_lmax)) return;
+    for (int i = 0; i < ns; ++i) {
+        const rt_sphere& s = scene->sphere_list[i];
+        if (!(std::isfinite(s.radius) && std::isfinite(s.center.e[0]) && std::isfinite(s.center.e[1]) &&
+              std::isfinite(s.center.e[2])))
+            return;
+    }
+    auto rad = [&](int i) { return std::fabs(scene->sphere_list[i].radius); };
+    std::vector<int> big;                        // the unflagged spheres (not the padding record)
+    for (int j = f.ns_merge; j < f.ns_pad; ++j)
+        if (hs.cand_orig[j] < ns) big.push_back(hs.cand_orig[j]);
+    const int m = std::min((int)big.size(), kMergeScan);
+    std::partial_sort(big.begin(), big.begin() + m, big.end(),
+                      [&](int x, int y) { return rad(x) != rad(y) ? rad(x) > rad(y) : x < y; });
+    long double sum[3] = {0.0L, 0.0L, 0.0L};
+    for (int i = 0; i < ns; ++i)
+        for (int a = 0; a < 3; ++a) sum[a] += scene->sphere_list[i].center.e[a];
+    std::vector<char> used((size_t)ns, 0);
+    std::vector<int> front;
+    for (int ii = 0; ii < m; ++ii) {
+        const int i = big[ii];
+        if (used[i]) continue;
+        int best = -1;
+        double cbest = HUGE_VAL;
+        for (int jj = ii + 1; jj < m; ++jj) {
+            const int j = big[jj];
+            if (used[j]) continue;
+            const rt_sphere &p = scene->sphere_list[i], &q = scene->sphere_list[j];
+            double d2 = 0.0, uv = 0.0, uu = 0.0, vv = 0.0;
+            for (int a = 0; a < 3; ++a) {
+                const double P = (double)((sum[a] - p.center.e[a] - q.center.e[a]) / (ns - 2));
+                const double u = p.center.e[a] - P, v = q.center.e[a] - P;
+                d2 += (p.center.e[a] - q.center.e[a]) * (p.center.e[a] - q.center.e[a]);
+                uv += u * v;
+                uu += u * u;
+                vv += v * v;
+            }
+            const double rs = rad(i) + rad(j);
+            if (!(d2 > rs * rs * (1.0 + 0x1p-12)) || !(uu > rad(i) * rad(i)) || !(vv > rad(j) * rad(j))) continue;
+            const double c = uv / std::sqrt(uu * vv);           // (overflow: NaN, never the smallest)
+            if (c < cbest) {
+                cbest = c;
+                best = j;
+            }
+        }
+        if (best >= 0 && cbest <= kFwdCos) {
+            used[i] = used[best] = 1;
+            front.push_back(i);
+            front.push_back(best);
+        }
+    }
+    if (front.empty()) return;
+    // the unflagged records again: the pairs, then the others as they were
+    std::vector<int> slot_of((size_t)f.ns_pad, -1), order(front);
+    for (int j = f.ns_merge; j < f.ns_pad; ++j) {
+        slot_of[(size_t)hs.cand_orig[j]] = j;
+        if (hs.cand_orig[j] >= ns || !used[hs.cand_orig[j]]) order.push_back(hs.cand_orig[j]);
+    }
+    const std::vector<SphCand> cand(hs.sph_cand);
+    const std::vector<SphGeo> slot(hs.sph_slot);
+    for (size_t k = 0; k < order.size(); ++k) {
+        const size_t to = (size_t)f.ns_merge + k, from = (size_t)slot_of[(size_t)order[k]];
+        hs.cand_orig[to] = order[k];
+        hs.sph_cand[to] = cand[from];
+        hs.sph_slot[to] = slot[from];
+    }
+    f.ns_fwd = (int)front.size();
 }
 
 }  // namespace rt

@@ -20,6 +20,7 @@ struct SceneFacts {
     long long n_texels = 0;
     double cand_lmax = HUGE_VAL;     // KParams::cand_lmax
     int ns_merge = 0;                // leading candidate records that are flagged pairs
+    int ns_fwd = 0;                  // ... and the records after them that are forward pairs
     double cbb[6] = {0, 0, 0, 0, 0, 0};   // triangles' box (RT_SEM_CUDA hit_BBox)
     int sky_w = 0, sky_h = 0;
     int bvh_nodes = 0, bvh_depth = 0, bvh_stack4 = 0;
@@ -41,7 +42,7 @@ struct SceneFacts {
 template <template <class> class Array>
 struct SceneArrays {
     Array<SphGeo> sph;               // [ns_pad], the caller's order
-    Array<SphCand> sph_cand;         // [ns_pad], candidate-record order (order_candidates)
+    Array<SphCand> sph_cand;         // [ns_pad], candidate-record order (order_candidates, pair_forward)
     Array<int> cand_orig;            // the sphere index of each candidate record
     Array<SphGeo> sph_slot;          // sph in candidate-record order
     Array<DevMat> sph_mat;
@@ -67,5 +68,8 @@ struct HostScene : SceneArrays<HostArray> {
 // Fills `out` from a scene that passed validation.  RT_OK, or RT_EUNSUPPORTED
 // with `err` set (2^31 texels or more; mat_list is then not read).
 int prepare_scene(const rt_scene* scene, HostScene& out, std::string& err);
+// Chooses the forward pairs of a prepared scene and moves their candidate
+// records behind the flagged ones (facts.ns_fwd; rt_scene_prep.cpp).  Host only.
+void pair_forward(const rt_scene* scene, HostScene& hs);
 
 }  // namespace rt

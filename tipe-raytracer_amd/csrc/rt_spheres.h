@@ -137,6 +137,12 @@ __device__ __forceinline__ void dmin_acc(double& a, double b)
     asm("v_min_f64 %0, %0, %1" : "+v"(a) : "v"(b));
 }
 
+// a = min(a, |b|) in a's own register (dmin_abs2's conditions, dmin_acc's reason)
+__device__ __forceinline__ void dmin_abs_acc(double& a, double b)
+{
+    asm("v_min_f64 %0, %0, |%1|" : "+v"(a) : "v"(b));
+}
+
 // main.c:214's `r.x > 0.5 || r.y > 0.5 || r.z > 0.5` as max(x, y, z) > 0.5
 // (a NaN component drops out of v_max_f64 exactly as it fails its own
 // comparison; the throughputs are arithmetic results, never signalling
@@ -149,10 +155,11 @@ __device__ __forceinline__ bool any_above_half(V3 r)
 
 #if RT_DIAG_MERGE
 // tools/merge_share.py: flagged pairs that took one tail [0] / two tails [4],
-// per wave of the block (every active lane adds the same wave-uniform step)
+// forward pairs likewise [8] / [12], per wave of the block (every active lane
+// adds the same wave-uniform step)
 __device__ __forceinline__ unsigned* diag_merge()
 {
-    __shared__ unsigned dm_lds[8];
+    __shared__ unsigned dm_lds[16];
     return dm_lds + (threadIdx.x >> 6);
 }
 #endif
@@ -274,6 +281,94 @@ __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, co
             bn2 = dmin_raw(bn2, dmax_raw(bn, nc));
             bn = dmin_raw(bn, nc);
             if (!merged) {
+                const double nb = cand_tail<AMGM>(h1, D1, thrM, k + 1, msk);
+                dmin_acc(bn2, dmax_raw(bn, nb));
+                dmin_acc(bn, nb);
+            }
+        }
+        // Forward pairs, records [ns_merge, ns_merge + ns_fwd): two spheres that a
+        // ray starting between them moves towards at most one of (the README
+        // box's opposite walls: D > 0 for both on almost every ray, so the test
+        // above never merges them).  A lane's sphere is dead when
+        //   h > hmin  and  ca > -cmin        (the computed h and ca of this scan)
+        // and live otherwise, whatever its D; the wave merges when no lane is
+        // live for both, and the one tail runs on the lane's live sphere (sphere
+        // 0 when neither is; the choice goes into the tag's low bit).  With hmin =
+        // 2^-16 Hs and cmin = 2^-44 Hs^2, and on rays with thrM >= 2^-26 Hs only
+        // (else hthr lets no lane certify; that covers thrM < 0), a dead
+        // sphere's tail only writes a sentinel: D =
+        // fl(h^2 - ca) <= (h^2 + cmin)(1 + u); D <= 0 or NaN gives the sentinel as
+        // above; else sa <= sqrt(D)(1 + 2^-45) <= (h + cmin / 2h)(1 + 2^-44), and
+        // with hmin < h <= 1.01 Hs
+        //   n1 = -h - sa < -hmin < 0 < thrM                  (r1 is false: n = n2)
+        //   n2 = fl(sa - h) <= cmin / 2hmin + 2^-43 Hs = (2^-29 + 2^-43) Hs,
+        // which with the scan's whole root error 2^-29.29 Hs on top stays below
+        // 2^-27 Hs < thrM, so n >= thrM fails.  cmin is 9.8 x the 2^-47.3 Hs^2 error
+        // of ca: a ray leaving the wall it sits on, its ca rounding noise around
+        // 0, certifies.  Both tests read high words only, and the thresholds
+        // are the high words of Hs and Hs^2 with the exponent field lowered (Hs
+        // >= 2^-71 on a fast ray, so nothing borrows out of it; other rays are
+        // ambiguous up front, as are those with a NaN or infinite h or ca, which
+        // can pass): hi(h) > hi(hmin) as signed ints -- a negative h has a
+        // negative high word and fails, and two positive doubles with different
+        // high words order as those do, so it implies h > hmin; (unsigned) hi(ca)
+        // < 2^31 + hi(cmin) -- every ca >= 0 has a high word below 2^31 and
+        // passes, and a negative ca has 2^31 + hi(|ca|), which grows with |ca|
+        // (signed order reverses below zero, unsigned order of the magnitudes
+        // does not), so it passes only with hi(|ca|) < hi(cmin), which implies
+        // |ca| < cmin.
+        // A dead sphere is dropped altogether, its D from the grazing test too
+        // (the chosen sphere's h and ca are selected, and D follows): the
+        // reference itself cannot hit it.  Its own h and D are within 16u Hs and
+        // 2^-47.3 Hs^2 of the ones here (the bound above, which does not ask for
+        // D >= T1), so D_ref <= h^2 + (2^-44 + 2^-47.2) Hs^2, its first root is
+        // negative, and its second, sqrt(D_ref) - h_ref <= 1.11 x 2^-44 Hs^2 /
+        // (2 x 2^-16 Hs) + 2^-48 Hs < 2^-28 Hs, is below thr - M: t2 < 1e-4.  So
+        // fewer rays rescan than with both D in gmin; the winner is the same.
+        constexpr double fwd_h = 1.0 / (double)(1ull << RT_FWD_HEXP), fwd_c = 1.0 / (double)(1ull << RT_FWD_CEXP);
+        static_assert(RT_FWD_HEXP >= 8 && RT_FWD_HEXP <= 24 && fwd_c >= 0x1p-46 &&
+                          fwd_c / (2.0 * fwd_h) + 0x1p-29 + 0x1p-43 <= RT_CAND_M / 2,
+                      "forward pairs: cmin must exceed 2 x ca's error 2^-47.3 Hs^2 and the dead root stay below thrM / 2");
+        const int hthr = thrM >= Hs * RT_CAND_M ? (int)((uint32_t)__double2hiint(Hs) - ((uint32_t)RT_FWD_HEXP << 20))
+                                                : 0x7fffffff;
+        const uint32_t cthr = (uint32_t)__double2hiint(Hs2) + (0x80000000u - ((uint32_t)RT_FWD_CEXP << 20));
+        for (const int kf = kp.ns_merge + kp.ns_fwd; k < kf; k += 2) {
+            double g[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) g[j] = sc[4 * k + j];
+            const double h0 = fma(-g[2], d.z, fma(-g[1], d.y, fma(-g[0], d.x, od)));
+            const double ca0 = fma(g[2], oaz, fma(g[1], oay, fma(g[0], oax, fma(a, g[3], aoo))));
+            double h1 = fma(-g[6], d.z, fma(-g[5], d.y, fma(-g[4], d.x, od)));
+            double ca1 = fma(g[6], oaz, fma(g[5], oay, fma(g[4], oax, fma(a, g[7], aoo))));
+            asm("" : "+v"(h1), "+v"(ca1));
+            // (a ballot per comparison: one ballot of the combined predicate goes
+            // through a v_cndmask and a v_cmp_ne)
+            const bool lh0 = __double2hiint(h0) <= hthr, lc0 = (uint32_t)__double2hiint(ca0) >= cthr;
+            const bool lh1 = __double2hiint(h1) <= hthr, lc1 = (uint32_t)__double2hiint(ca1) >= cthr;
+            const uint64_t l1 = __builtin_amdgcn_ballot_w64(lh1) | __builtin_amdgcn_ballot_w64(lc1);
+            const bool merged = ((__builtin_amdgcn_ballot_w64(lh0) | __builtin_amdgcn_ballot_w64(lc0)) & l1) == 0;
+#if RT_DIAG_MERGE
+            diag_merge()[merged ? 8 : 12] += 1u;
+#endif
+            const bool sel = merged && (lh1 || lc1);
+            // D and the grazing test of the chosen sphere only: the reference
+            // itself misses a dead sphere (above), grazing or not
+            const double hs = sel ? h1 : h0, cas = sel ? ca1 : ca0;
+            const double Ds = fma(hs, hs, -cas);
+            dmin_abs_acc(gmin, Ds);
+            double nc = cand_tail<AMGM>(hs, Ds, thrM, k, msk);
+            // the choice into the tag's low bit, as the carry-in of one add
+            uint32_t lo;
+            asm("v_addc_co_u32_e64 %0, vcc, 0, %1, %2"
+                : "=v"(lo)
+                : "v"((uint32_t)__double2loint(nc)), "s"(merged ? l1 : (uint64_t)0)
+                : "vcc");
+            nc = __hiloint2double(__double2hiint(nc), (int)lo);
+            bn2 = dmin_raw(bn2, dmax_raw(bn, nc));
+            bn = dmin_raw(bn, nc);
+            if (!merged) {
+                const double D1 = fma(h1, h1, -ca1);
+                dmin_abs_acc(gmin, D1);
                 const double nb = cand_tail<AMGM>(h1, D1, thrM, k + 1, msk);
                 dmin_acc(bn2, dmax_raw(bn, nb));
                 dmin_acc(bn, nb);

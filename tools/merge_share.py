@@ -6,7 +6,8 @@
 
 The diagnostic build counts, per wave, the flagged pairs that took the merged
 form and those that fell back to two tails, and writes both into the wave's
-RT_QUEUE_TRACE record (in place of rounds and tasks).  One JSON line per scene."""
+RT_QUEUE_TRACE record (in place of rounds and tasks), and the same two counts
+of the forward pairs (in place of the two clocks).  One JSON line per scene."""
 import json
 import os
 import sys
@@ -39,9 +40,12 @@ def run(kind, spp):
     d = np.fromfile(path, dtype=np.uint64).reshape(-1, 4)
     w = d[::64].astype(np.float64)               # the counts are wave-uniform: lane 0 of each wave
     one, two = float(w[:, 2].sum()), float(w[:, 3].sum())
+    f_one, f_two = float(w[:, 0].sum()), float(w[:, 1].sum())
     os.remove(path)
     return {"scene": kind, "spp": spp, "kernel": tipe_rt.last_render_kernel(), "flagged_pair_casts": one + two,
-            "one_tail": one, "two_tails": two, "merged_share": round(one / max(one + two, 1.0), 4)}
+            "one_tail": one, "two_tails": two, "merged_share": round(one / max(one + two, 1.0), 4),
+            "forward_pair_casts": f_one + f_two, "forward_one_tail": f_one, "forward_two_tails": f_two,
+            "forward_merged_share": round(f_one / max(f_one + f_two, 1.0), 4)}
 
 
 if __name__ == "__main__":

@@ -2,6 +2,8 @@
 // stdin, prepares it and prints one JSON line with the SceneFacts fields and,
 // per array, its element count, a 64-bit FNV-1a hash of its bytes and (up to
 // argv[1] elements, default 64; never for the BVH nodes) its contents.
+// argv[2] "fwd": pair_forward runs on the prepared scene first, as in
+// rt_scene_upload (tests/test_forward_pairs_host.py).
 // Input, whitespace-separated, numbers as strtod reads them (inf, nan, hex):
 //   spheres N            then N x: cx cy cz radius MAT
 //   triangles N tw th nm then N x: A(3) B(3) C(3) uvA(2) uvB(2) uvC(2) quelMat MAT
@@ -200,6 +202,7 @@ int main(int argc, char** argv)
         std::printf("{\"rc\": %d, \"error\": \"%s\"}\n", rc, err.c_str());
         return 0;
     }
+    if (argc > 2 && !std::strcmp(argv[2], "fwd")) pair_forward(&sc, hs);
     const SceneFacts& f = hs.facts;
     std::printf("{\"rc\": 0, ");
     fact("ns", f.ns);
@@ -210,6 +213,7 @@ int main(int argc, char** argv)
     fact("n_texels", f.n_texels);
     fact("cand_lmax", f.cand_lmax);
     fact("ns_merge", f.ns_merge);
+    fact("ns_fwd", f.ns_fwd);
     for (int i = 0; i < 6; ++i) fact(("cbb" + std::to_string(i)).c_str(), f.cbb[i]);
     fact("sky_w", f.sky_w);
     fact("sky_h", f.sky_h);
