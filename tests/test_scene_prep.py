@@ -1,16 +1,19 @@
 """Host check of the scene preparation (rt_scene_prep.cpp prepare_scene), CPU only.
 
 Everything rt_scene_upload copies to the device is prepared by one pure host
-function: the candidate records and their pairing order (order_candidates),
+function: the candidate records and their pairing order (pair_candidates),
 cand_lmax, the per-triangle precomputation and the affine texel map
 (tri_uv_affine), tex0, the BVH reorder and the bounds and flags the launch
 gates read.  tools/probes/scene_prep_check.cpp reads a scene as text, calls
 prepare_scene and prints the SceneFacts fields and the arrays as one JSON line;
 this test builds it with g++ and checks the cases below.  The expected pairing
-orders follow the rule in order_candidates' comment: among the spheres of
-smallest radius, in ascending radius (ties by index), each unpaired sphere
-takes the unpaired partner with the smallest x = (max(R_i, R_j) / d)^2 and the
-pair is flagged when x <= 1/16.
+orders follow the two rules in pair_candidates' comment.  Flagged pairs: among
+the spheres of smallest radius, in ascending radius (ties by index), each
+unpaired sphere takes the unpaired partner with the smallest
+x = (max(R_i, R_j) / d)^2 and the pair is flagged when x <= 1/16.  Forward
+pairs, among the spheres that are left: two disjoint spheres whose centres are
+nearly opposite (cosine <= -0.9) seen from the centroid P of all other spheres'
+centres, with P outside both.  The other spheres follow in the caller's order.
 """
 import json
 import math
@@ -83,17 +86,24 @@ ODD_COUNT = README + [((-0.3, 0.3, -2.0), 0.3, M((0, 1, 0), refl=0.5))]         
 SMALL_ONLY = [r for r in README if r[1] != 500] + [((0.0, 0.2, -2.0), 0.3, M((0.8, 0.8, 0.8)))]
 
 
-def check_order(checker, rows, rec, order, ns_merge):
+def check_order(checker, rows, rec, order, ns_merge, ns_fwd):
     ns, ns_pad = len(rows), (len(rows) + 1) & ~1
-    assert (rec["ns"], rec["ns_pad"], rec["ns_merge"]) == (ns, ns_pad, ns_merge)
+    assert (rec["ns"], rec["ns_pad"], rec["ns_merge"], rec["ns_fwd"]) == (ns, ns_pad, ns_merge, ns_fwd)
     assert rec["cand_orig"]["data"] == order and sorted(order) == list(range(ns_pad))
     # sph in the caller's order (r2 = radius^2, the padding's -inf)
     want = [[*c, r * r] for c, r, _ in rows] + [[0.0, 0.0, 0.0, -INF]] * (ns_pad - ns)
     assert rec["sph"]["data"] == want
     assert rec["sph_slot"]["data"] == [want[j] for j in order]
-    # the candidate records are the by-sphere records (RT_CAND_MERGE=off keeps them in place), permuted
-    by_sphere = run(checker, scene_text(rows), merge="off")["sph_cand"]["data"]
+    # the candidate records are the by-sphere records (RT_CAND_MERGE=off keeps them in place), permuted;
+    # the pairing changes nothing else
+    off = run(checker, scene_text(rows), merge="off")
+    by_sphere = off["sph_cand"]["data"]
+    assert (off["ns_merge"], off["ns_fwd"]) == (0, 0) and off["cand_orig"]["data"] == list(range(ns_pad))
     assert rec["sph_cand"]["data"] == [by_sphere[j] for j in order]
+    assert off["sph_slot"]["data"] == want
+    for key in rec:
+        if key not in ("ns_merge", "ns_fwd", "cand_orig", "sph_cand", "sph_slot", "facts_bits"):
+            assert rec[key] == off[key], key
     for (c, r, _), k in zip(rows, by_sphere):
         assert k[:3] == list(c) and k[3] == pytest.approx(sum(x * x for x in c) - r * r, rel=1e-12, abs=1e-12)
     if ns < ns_pad:
@@ -105,9 +115,19 @@ def pair_x(rows, i, j):
     return max(rows[i][1], rows[j][1]) ** 2 / d2
 
 
+NAN = float("nan")
+GREY = M((0.8, 0.8, 0.8))
+LEFT, FLOOR, RIGHT, BACK, CEILING, MIRROR = 0, 1, 2, 7, 8, 9
+
+
+def pairs(rec, lo, hi):
+    order = rec["cand_orig"]["data"]
+    return [tuple(order[k:k + 2]) for k in range(lo, hi, 2)]
+
+
 def test_readme_box_pairs(checker):
     rec = run(checker, scene_text(README))
-    check_order(checker, README, rec, [3, 6, 4, 5, 0, 1, 2, 7, 8, 9], 4)
+    check_order(checker, README, rec, [3, 6, 4, 5, 0, 2, 1, 8, 7, 9], 4, 4)
     assert pair_x(README, 3, 6) == pytest.approx(0.0218, abs=5e-5)
     assert pair_x(README, 4, 5) == pytest.approx(0.0269, abs=5e-5)
     assert math.isfinite(rec["cand_lmax"]) and rec["cand_lmax"] >= 1004.0
@@ -117,13 +137,100 @@ def test_readme_box_pairs(checker):
 
 def test_odd_count_shares_the_padding(checker):
     rec = run(checker, scene_text(ODD_COUNT))
-    check_order(checker, ODD_COUNT, rec, [10, 5, 3, 6, 4, 9, 0, 11, 1, 2, 7, 8], 8)
+    check_order(checker, ODD_COUNT, rec, [10, 5, 3, 6, 4, 9, 0, 11, 1, 8, 2, 7], 8, 2)
     slot = rec["cand_orig"]["data"].index(11)
     assert rec["sph_cand"]["data"][slot][3] == INF and rec["sph"]["data"][11][3] == -INF
 
 
 def test_small_only_flags_every_pair(checker):
-    check_order(checker, SMALL_ONLY, run(checker, scene_text(SMALL_ONLY)), [5, 3, 0, 2, 1, 4], 6)
+    check_order(checker, SMALL_ONLY, run(checker, scene_text(SMALL_ONLY)), [5, 3, 0, 2, 1, 4], 6, 0)
+
+
+def test_readme_box_wall_pairs(checker):
+    rec = run(checker, scene_text(README))
+    assert (rec["ns_merge"], rec["ns_fwd"]) == (4, 4)
+    assert pairs(rec, 0, 4) == [(3, 6), (4, 5)]                       # the two small pairs come first
+    assert pairs(rec, 4, 8) == [(LEFT, RIGHT), (FLOOR, CEILING)]
+    assert rec["cand_orig"]["data"][8:] == [BACK, MIRROR]             # unflagged, in the caller's order
+    assert sorted(rec["cand_orig"]["data"]) == list(range(10))
+    # against the unpaired run: the records are its records permuted by cand_orig, nothing else differs
+    off = run(checker, scene_text(README), merge="off")
+    assert rec["sph_cand"]["data"] == [off["sph_cand"]["data"][j] for j in rec["cand_orig"]["data"]]
+    assert rec["sph_slot"]["data"] == [off["sph_slot"]["data"][j] for j in rec["cand_orig"]["data"]]
+    assert off["sph_slot"]["data"] == off["sph"]["data"]
+    for key in rec:
+        if key not in ("ns_merge", "ns_fwd", "cand_orig", "sph_cand", "sph_slot", "facts_bits"):
+            assert rec[key] == off[key], key
+
+
+# Two radius-3 spheres on the x axis with two more on the z axis, whose centroid P = (0, 0.2, 0)
+# lies between the first two and off their axis; (2, 3) become a small pair (x = 9/256).
+def between(gap):
+    return [((-3.0 - gap, 0.0, 0.0), 3.0, GREY), ((3.0 + gap, 0.0, 0.0), 3.0, GREY),
+            ((0.0, 0.2, 8.0), 3.0, GREY), ((0.0, 0.2, -8.0), 3.0, GREY)]
+
+
+def test_disjoint_spheres_around_the_centroid_pair(checker):
+    rec = run(checker, scene_text(between(0.01)))
+    assert (rec["ns_merge"], rec["ns_fwd"]) == (2, 2)
+    assert pairs(rec, 0, 4) == [(2, 3), (0, 1)]
+
+
+def test_touching_spheres_get_no_forward_pair(checker):
+    rec = run(checker, scene_text(between(0.0)))                      # they touch at the origin, P is 0.2 off it
+    assert (rec["ns_merge"], rec["ns_fwd"]) == (2, 0)
+    assert rec["cand_orig"]["data"] == [2, 3, 0, 1]
+
+
+def test_nested_spheres_get_no_forward_pair(checker):
+    # the radius-4 sphere lies inside the radius-10 one; (2, 3) become a small pair (x = 16/576), and their
+    # centroid P = (2.5, 0.1, 0) is between the two centres that are left, inside the large sphere
+    rows = [((0.0, 0.0, 0.0), 10.0, GREY), ((5.0, 0.0, 0.0), 4.0, GREY),
+            ((2.5, 0.1, 12.0), 4.0, GREY), ((2.5, 0.1, -12.0), 4.0, GREY)]
+    rec = run(checker, scene_text(rows))
+    assert (rec["ns_merge"], rec["ns_fwd"]) == (2, 0)
+    assert rec["cand_orig"]["data"] == [2, 3, 0, 1]
+    # ... and overlapping: the same spheres as the disjoint case, pushed into each other
+    assert run(checker, scene_text(between(-0.5)))["ns_fwd"] == 0
+
+
+def test_a_nan_centre_gets_no_pair(checker):
+    rows = between(0.01) + [((NAN, 0.0, 0.0), 1.0, GREY)]
+    rec = run(checker, scene_text(rows))
+    assert (rec["ns_merge"], rec["ns_fwd"]) == (0, 0)
+    assert rec["cand_orig"]["data"] == list(range(6))
+
+
+def forty_spheres():
+    """Six radius-500 walls around 34 small spheres of radius 0.2 to 0.8: more than kMergeScan (32) spheres."""
+    state = [20260101]
+
+    def rnd():                                   # a 31-bit LCG: the scene does not depend on a library's stream
+        state[0] = (state[0] * 1103515245 + 12345) % (1 << 31)
+        return state[0] / float(1 << 31)
+
+    rows, walls = [], 0
+    for i in range(40):
+        if i % 7 == 3 and walls < 6:
+            c = [0.0, 0.0, 0.0]
+            c[walls // 2] = 504.0 if walls % 2 else -504.0
+            rows.append((tuple(c), 500.0, GREY))
+            walls += 1
+        else:
+            rows.append((tuple(round(8.0 * rnd() - 4.0, 3) for _ in range(3)), (0.2, 0.3, 0.5, 0.8)[int(4 * rnd())], GREY))
+    return rows
+
+
+def test_more_spheres_than_the_scan_looks_at(checker):
+    # 34 small spheres, of which the flagged-pair rule scans the 32 smallest: 27 and 29 (radius 0.8) stay
+    # unflagged.  The expected order and counts were recorded from the two-step host code this step replaced
+    # (prepare_scene, then pair_forward), not from pair_candidates.
+    rows = forty_spheres()
+    assert len(rows) == 40 and sum(r == 500.0 for _, r, _ in rows) == 6
+    rec = run(checker, scene_text(rows))
+    check_order(checker, rows, rec,
+                [6, 16, 8, 19, 21, 30, 23, 11, 33, 28, 5, 20, 7, 25, 12, 32, 18, 0, 36, 14, 1, 4, 9, 13, 15, 34, 35, 26,
+                 37, 22, 3, 10, 17, 24, 31, 38, 2, 39, 27, 29], 30, 8)
 
 
 @pytest.mark.parametrize("mode,rows", [("all", README), ("off", README), ("all", ODD_COUNT), ("off", ODD_COUNT)])
@@ -132,6 +239,14 @@ def test_cand_merge_override_keeps_the_callers_order(checker, mode, rows):
     ns_pad = (len(rows) + 1) & ~1
     assert rec["cand_orig"]["data"] == list(range(ns_pad))
     assert rec["ns_merge"] == (ns_pad if mode == "all" else 0)
+    assert rec["ns_fwd"] == 0
+
+
+@pytest.mark.parametrize("mode,want", [("fwd-all", (0, 10)), ("all", (10, 0)), ("off", (0, 0))])
+def test_cand_merge_modes(checker, mode, want):
+    rec = run(checker, scene_text(README), merge=mode)
+    assert (rec["ns_merge"], rec["ns_fwd"]) == want
+    assert rec["cand_orig"]["data"] == list(range(10))
 
 
 @pytest.mark.parametrize("extra,sph_bound", [
@@ -142,7 +257,7 @@ def test_cand_merge_override_keeps_the_callers_order(checker, mode, rows):
 def test_non_finite_sphere_switches_the_pass_off(checker, extra, sph_bound):
     rows = README + [(extra[0], extra[1], M((1, 0, 0)))]
     rec = run(checker, scene_text(rows))
-    assert rec["ns_merge"] == 0 and rec["cand_orig"]["data"] == list(range(12))
+    assert rec["ns_merge"] == 0 and rec["ns_fwd"] == 0 and rec["cand_orig"]["data"] == list(range(12))
     assert rec["cand_lmax"] == INF and rec["coord_max"] == INF
     assert rec["sph_bound"] == sph_bound
 

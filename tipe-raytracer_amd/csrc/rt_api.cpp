@@ -450,7 +450,6 @@ int rt_scene_upload(int device, const rt_scene* scene, rt_device_scene** out)
     HostScene hs;
     std::string err;
     if ((rc = prepare_scene(scene, hs, err))) return fail(rc, "%s", err.c_str());
-    pair_forward(scene, hs);
     rt_device_scene* ds = new rt_device_scene();
     ds->device = device;
     ds->facts = hs.facts;

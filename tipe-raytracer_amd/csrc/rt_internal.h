@@ -7,7 +7,7 @@
 //                          scanned wave-uniformly through the scalar unit,
 //                          two records per s_load_dwordx16; padded to an even
 //                          count with never-hit records (k = +inf); in the
-//                          host's pairing order (rt_scene_prep.cpp order_candidates)
+//                          host's pairing order (rt_scene_prep.cpp pair_candidates)
 //   int     [ns_pad]       the sphere index of each candidate record, and
 //   SphGeo  [ns_pad]       its SphGeo (the candidate pass's winner)
 //   SphGeo  [ns_pad] 32 B  center, radius^2 — the exact reference test
@@ -167,8 +167,8 @@ struct KParams {
     float bvh_rb_f;          // a float with rb_f (1 + 2^-23) <= R_b (the walk's cheap "inside" test)
     int bvh_far;             // some ray origin may lie beyond R_b: a sphere or the camera does
     int ns_merge;            // the first ns_merge (even) candidate records are pairs that may share one
-                             // root tail (rt_scene_prep.cpp order_candidates; a hint, any value gives the same result)
-    int ns_fwd;              // the next ns_fwd (even) records are forward pairs, which share it by another test (pair_forward)
+                             // root tail (rt_scene_prep.cpp pair_candidates; a hint, any value gives the same result)
+    int ns_fwd;              // the next ns_fwd (even) records are forward pairs, which share it by another test
                              // (a hint as well; in the padding before cand_orig: no field moves)
     const int* cand_orig;    // [ns_pad] candidate record (slot) j describes sphere cand_orig[j] of sph
     const SphGeo* sph_slot;  // [ns_pad] sph[cand_orig[j]]: the candidate pass's winner retest

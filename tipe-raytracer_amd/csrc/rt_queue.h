@@ -417,10 +417,10 @@ void render_kernel_q(const KParams kp)
     diag_cnt()[256] = 0u;
 #endif
 #if RT_DIAG_MERGE
-    diag_merge()[0] = 0u;
-    diag_merge()[4] = 0u;
-    diag_merge()[8] = 0u;
-    diag_merge()[12] = 0u;
+    diag_merge()[DM_FLAGGED_ONE] = 0u;
+    diag_merge()[DM_FLAGGED_TWO] = 0u;
+    diag_merge()[DM_FORWARD_ONE] = 0u;
+    diag_merge()[DM_FORWARD_TWO] = 0u;
 #endif
     int x = 0, g = 0, s1 = 0;
     int node = 0, sp = 0, win_orig = 0;      // BVH walk in flight (state SM_TRAV)
@@ -763,10 +763,10 @@ void render_kernel_q(const KParams kp)
         q[3] = diag_cnt()[256];
 #endif
 #if RT_DIAG_MERGE
-        q[2] = diag_merge()[0];      // diagnostic: the wave's flagged pairs with one tail, with two
-        q[3] = diag_merge()[4];
-        q[0] = diag_merge()[8];      // ... and its forward pairs (in place of the clocks)
-        q[1] = diag_merge()[12];
+        q[2] = diag_merge()[DM_FLAGGED_ONE];     // diagnostic: the wave's flagged pairs with one tail, with two
+        q[3] = diag_merge()[DM_FLAGGED_TWO];
+        q[0] = diag_merge()[DM_FORWARD_ONE];     // ... and its forward pairs (in place of the clocks)
+        q[1] = diag_merge()[DM_FORWARD_TWO];
 #endif
 #if RT_PHASE_CLOCK
         for (int k = 0; k < 5; ++k) q[4 + k] = ph[k];

@@ -141,16 +141,79 @@ double sphere_bound(const rt_sphere& q)
     return std::isfinite(b) ? b : HUGE_VAL;
 }
 
-// The order of the candidate records and how many leading ones are pairs
-// that may share one root tail (rt_spheres.h spheres_closest; KParams::
-// ns_merge).  The kernel merges a flagged pair's tails in a wave-cast in which
-// no lane's line crosses both spheres, and pays about nine cheap VALU
+// ---- The order of the candidate records (pair_candidates) ----
+// The order and how many leading records are pairs that may share one root
+// tail (rt_spheres.h spheres_closest): KParams::ns_merge flagged pairs, then
+// KParams::ns_fwd forward pairs.  All of it is a performance hint: the pass
+// gives the same winner for every order and every count (order[] goes to the
+// device as KParams::cand_orig, which turns the winning record's slot back
+// into the caller's sphere index); a wrongly flagged pair costs its test,
+// never the result.
+
+// RT_CAND_MERGE (tests, A/B runs): "off" flags no pair, "all" makes every pair
+// of the caller's order a flagged pair, "fwd-all" every pair a forward pair --
+// the results must not notice.
+enum class PairMode { kHost, kOff, kAll, kFwdAll };
+PairMode pair_mode()
+{
+    const char* mode = std::getenv("RT_CAND_MERGE");
+    if (mode && !std::strcmp(mode, "off")) return PairMode::kOff;
+    if (mode && !std::strcmp(mode, "all")) return PairMode::kAll;
+    if (mode && !std::strcmp(mode, "fwd-all")) return PairMode::kFwdAll;
+    return PairMode::kHost;
+}
+
+// Both rules look at kMergeScan spheres: the unpaired ones of smallest or of
+// largest radius, in that order (ties by index).
+constexpr int kMergeScan = 32;
+std::vector<int> scan_list(const rt_scene* scene, const std::vector<char>& used, bool largest)
+{
+    auto rad = [&](int i) { return std::fabs(scene->sphere_list[i].radius); };
+    std::vector<int> list;
+    for (int i = 0; i < scene->nbSpheres; ++i)
+        if (!used[i]) list.push_back(i);
+    const int m = std::min((int)list.size(), kMergeScan);
+    std::partial_sort(list.begin(), list.begin() + m, list.end(), [&](int x, int y) {
+        return rad(x) != rad(y) ? (largest ? rad(x) > rad(y) : rad(x) < rad(y)) : x < y;
+    });
+    list.resize((size_t)m);
+    return list;
+}
+
+// Both rules pair greedily: in the list's order each unpaired sphere takes the
+// unpaired partner after it with the smallest score, and the two are appended
+// to `order` as a pair when that score is at most `limit`.  A pair that is not
+// eligible scores +inf or NaN, which is never the smallest.
+template <class Score>
+void pair_greedy(const std::vector<int>& list, Score score, double limit, std::vector<char>& used,
+                 std::vector<int>& order)
+{
+    for (size_t ii = 0; ii < list.size(); ++ii) {
+        const int i = list[ii];
+        if (used[i]) continue;
+        int best = -1;
+        double sbest = HUGE_VAL;
+        for (size_t jj = ii + 1; jj < list.size(); ++jj) {
+            const int j = list[jj];
+            if (used[j]) continue;
+            const double s = score(i, j);
+            if (s < sbest) {
+                sbest = s;
+                best = j;
+            }
+        }
+        if (best >= 0 && sbest <= limit) {
+            used[i] = used[best] = 1;
+            order.push_back(i);
+            order.push_back(best);
+        }
+    }
+}
+
+// Flagged pairs.  The kernel merges a flagged pair's tails in a wave-cast in
+// which no lane's line crosses both spheres, and pays about nine cheap VALU
 // instructions for the test and the selects against a 15-instruction tail, so
 // a pair is worth flagging when that is the common case.
-// Both are a performance hint: the pass gives the same winner for every order
-// and every flag (order[] goes to the device as KParams::cand_orig, which
-// turns the winning record's slot back into the caller's sphere index).
-//
 // The rule: of the lines through the centre of one sphere the fraction
 // 1 - sqrt(1 - (R/d)^2) <= (R/d)^2 crosses a disjoint sphere of radius R whose
 // centre is d away.  Among the kMergeScan spheres of smallest radius (small
@@ -161,70 +224,89 @@ double sphere_bound(const rt_sphere& q)
 // radius-500 wall overlaps every other sphere and is never flagged).
 // Overlapping, touching and nested spheres have x > 1/16.  An odd count leaves
 // the never-hit padding record, which no line crosses: it is flagged with one
-// more sphere.  The other spheres follow in the caller's order.
-// finite: every sphere's centre and radius are finite (else no pair is flagged).
-constexpr int kMergeScan = 32;
-int order_candidates(const rt_scene* scene, int ns_pad, bool finite, std::vector<int>& order)
+// more sphere.
+//
+// Forward pairs.  The kernel merges such a pair's tails when no lane moves
+// towards both spheres, (o - C) . d < 0 for both, and a ray does that only
+// when its direction lies in the wedge between the two half-spaces whose
+// normals point from its origin to the two centres.  The wedge is thin when
+// the origin lies between the spheres: outside both, with the centres nearly
+// opposite.  The centroid P of all other spheres' centres stands for where rays
+// start (every ray but the camera's starts on a sphere).  Among the kMergeScan
+// unflagged spheres of largest radius (large spheres are the ones whose
+// D > 0 on most rays, which the first rule cannot merge), in descending
+// radius, each takes the unpaired partner with the smallest c = cos of the
+// angle C_i P C_j, among partners that are disjoint from it by a margin, d^2 >
+// (R_i + R_j)^2 (1 + 2^-12) (touching, overlapping and nested spheres have an
+// origin on or in one of them where a ray moves towards both in half of the
+// directions), with P outside both, and the pair is flagged when c <= -0.9.
+// P is a coarse stand-in, so the threshold is loose: the README box's left/right
+// and floor/ceiling walls give c = -0.9675 (its back wall drags P 64 units
+// behind the box), while two walls that meet in an edge give c near 0 and a
+// wall with a small sphere in front of it c > 0.9.
+//
+// The other spheres follow in the caller's order, the padding record last if
+// no pair took it.  finite: every sphere's centre and radius are finite (else
+// no pair of either kind); forward pairs also need three spheres and the
+// candidate pass switched on (a finite f.cand_lmax).
+void pair_candidates(const rt_scene* scene, bool finite, SceneFacts& f, std::vector<int>& order)
 {
-    const int ns = scene->nbSpheres;
+    const int ns = f.ns;
+    const rt_sphere* sph = scene->sphere_list;
+    auto rad = [&](int i) { return std::fabs(sph[i].radius); };
     order.clear();
-    std::vector<int> small((size_t)ns);
-    for (int i = 0; i < ns; ++i) small[i] = i;
-    auto rad = [&](int i) { return std::fabs(scene->sphere_list[i].radius); };
-    std::vector<char> used((size_t)ns, 0);
-    // RT_CAND_MERGE (tests, A/B runs): "off" flags no pair, "all" flags every
-    // pair ("fwd-all": none here, every pair a forward pair in pair_forward),
-    // all in the caller's order -- the results must not notice
-    const char* mode = std::getenv("RT_CAND_MERGE");
-    const bool all = mode && !std::strcmp(mode, "all"), off = mode && !std::strcmp(mode, "off");
-    const bool fwd_all = mode && !std::strcmp(mode, "fwd-all");
-    if (all || off || fwd_all) {
-        for (int i = 0; i < ns_pad; ++i) order.push_back(i);
-        return all ? ns_pad : 0;
+    f.ns_merge = f.ns_fwd = 0;
+    const PairMode mode = pair_mode();
+    if (mode != PairMode::kHost) {
+        for (int i = 0; i < f.ns_pad; ++i) order.push_back(i);
+        f.ns_merge = mode == PairMode::kAll ? f.ns_pad : 0;
+        f.ns_fwd = mode == PairMode::kFwdAll ? f.ns_pad : 0;
+        return;
     }
+    std::vector<char> used((size_t)ns, 0);
     if (finite) {
-        const int m = std::min(ns, kMergeScan);
-        std::partial_sort(small.begin(), small.begin() + m, small.end(),
-                          [&](int x, int y) { return rad(x) != rad(y) ? rad(x) < rad(y) : x < y; });
-        for (int ii = 0; ii < m; ++ii) {
-            const int i = small[ii];
-            if (used[i]) continue;
-            int best = -1;
-            double xbest = HUGE_VAL;
-            for (int jj = ii + 1; jj < m; ++jj) {
-                const int j = small[jj];
-                if (used[j]) continue;
-                const rt_sphere &p = scene->sphere_list[i], &q = scene->sphere_list[j];
-                double d2 = 0.0;
-                for (int a = 0; a < 3; ++a) d2 += (p.center.e[a] - q.center.e[a]) * (p.center.e[a] - q.center.e[a]);
-                const double rm = std::max(rad(i), rad(j));
-                const double x = rm * rm / d2;                  // (d = 0: +inf or NaN, never the smallest)
-                if (x < xbest) {
-                    xbest = x;
-                    best = j;
-                }
-            }
-            if (best >= 0 && xbest <= 1.0 / 16) {
-                used[i] = used[best] = 1;
-                order.push_back(i);
-                order.push_back(best);
-            }
-        }
-        if (ns < ns_pad) {                                      // odd count: one sphere shares the padding's pair
-            for (int ii = 0; ii < m; ++ii)
-                if (!used[small[ii]]) {
-                    used[small[ii]] = 1;
-                    order.push_back(small[ii]);
+        const std::vector<int> small = scan_list(scene, used, false);
+        pair_greedy(small, [&](int i, int j) {
+            double d2 = 0.0;
+            for (int a = 0; a < 3; ++a) d2 += (sph[i].center.e[a] - sph[j].center.e[a]) * (sph[i].center.e[a] - sph[j].center.e[a]);
+            const double rm = std::max(rad(i), rad(j));
+            return rm * rm / d2;                                // (d = 0: +inf or NaN)
+        }, 1.0 / 16, used, order);
+        if (ns < f.ns_pad) {                                    // odd count: one sphere shares the padding's pair
+            for (int i : small)
+                if (!used[i]) {
+                    used[i] = 1;
+                    order.push_back(i);
                     order.push_back(ns);
                     break;
                 }
         }
+        f.ns_merge = (int)order.size();
     }
-    const int ns_merge = (int)order.size();
+    if (finite && ns >= 3 && std::isfinite(f.cand_lmax)) {
+        long double sum[3] = {0.0L, 0.0L, 0.0L};
+        for (int i = 0; i < ns; ++i)
+            for (int a = 0; a < 3; ++a) sum[a] += sph[i].center.e[a];
+        pair_greedy(scan_list(scene, used, true), [&](int i, int j) {
+            const rt_sphere &p = sph[i], &q = sph[j];
+            double d2 = 0.0, uv = 0.0, uu = 0.0, vv = 0.0;
+            for (int a = 0; a < 3; ++a) {
+                const double P = (double)((sum[a] - p.center.e[a] - q.center.e[a]) / (ns - 2));
+                const double u = p.center.e[a] - P, v = q.center.e[a] - P;
+                d2 += (p.center.e[a] - q.center.e[a]) * (p.center.e[a] - q.center.e[a]);
+                uv += u * v;
+                uu += u * u;
+                vv += v * v;
+            }
+            const double rs = rad(i) + rad(j);
+            if (!(d2 > rs * rs * (1.0 + 0x1p-12)) || !(uu > rad(i) * rad(i)) || !(vv > rad(j) * rad(j))) return HUGE_VAL;
+            return uv / std::sqrt(uu * vv);                     // (overflow: NaN)
+        }, -0.9, used, order);
+        f.ns_fwd = (int)order.size() - f.ns_merge;
+    }
     for (int i = 0; i < ns; ++i)
         if (!used[i]) order.push_back(i);
-    if ((int)order.size() < ns_pad) order.push_back(ns);        // (the padding record was not placed above)
-    return ns_merge;
+    if ((int)order.size() < f.ns_pad) order.push_back(ns);      // (no pair took the padding record)
 }
 
 }  // namespace
@@ -290,7 +372,7 @@ int prepare_scene(const rt_scene* scene, HostScene& hs, std::string& err)
     bool coords_finite = spheres_finite;
     f.cand_lmax = std::isfinite((double)lmax) && ns <= 65534 ? std::nextafter((double)lmax, HUGE_VAL) : HUGE_VAL;
     // the candidate records in pairing order; SphGeo and the per-sphere tables keep the caller's
-    f.ns_merge = order_candidates(scene, f.ns_pad, spheres_finite, hs.cand_orig);
+    pair_candidates(scene, spheres_finite, f, hs.cand_orig);
     hs.sph_cand.resize((size_t)f.ns_pad);
     hs.sph_slot.resize((size_t)f.ns_pad);
     for (int j = 0; j < f.ns_pad; ++j) {
@@ -415,114 +497,6 @@ int prepare_scene(const rt_scene* scene, HostScene& hs, std::string& err)
     hs.bvh.swap(bvh.nodes4);
     hs.tri_orig.swap(bvh.order);
     return RT_OK;
-}
-
-// Forward pairs: the ns_fwd candidate records after the flagged ones
-// (rt_spheres.h spheres_closest; KParams::ns_fwd).  A step of its own after
-// prepare_scene, which keeps the order its rule gives (tests/test_scene_prep.py):
-// it moves the chosen pairs to the front of the unflagged records, in
-// cand_orig, sph_cand and sph_slot alike; the rest keep their order.  Like the
-// flags of order_candidates a performance hint only.
-// The kernel merges such a pair's tails when no lane moves
-// towards both spheres, (o - C) . d < 0 for both, and a ray does that only
-// when its direction lies in the wedge between the two half-spaces whose
-// normals point from its origin to the two centres.  The wedge is thin when
-// the origin lies between the spheres: outside both, with the centres nearly
-// opposite.  The centroid P of all other spheres' centres stands for where rays
-// start (every ray but the camera's starts on a sphere).  Among the kMergeScan
-// unflagged spheres of largest radius (large spheres are the ones whose
-// D > 0 on most rays, which order_candidates' rule cannot merge), in descending
-// radius, each takes the unpaired partner with the smallest c = cos of the
-// angle C_i P C_j, among partners that are disjoint from it by a margin, d^2 >
-// (R_i + R_j)^2 (1 + 2^-12) (touching, overlapping and nested spheres have an
-// origin on or in one of them where a ray moves towards both in half of the
-// directions), with P outside both, and the pair is flagged when c <= -0.9.
-// P is a coarse stand-in, so the threshold is loose: the README box's left/right
-// and floor/ceiling walls give c = -0.9675 (its back wall drags P 64 units
-// behind the box), while two walls that meet in an edge give c near 0 and a
-// wall with a small sphere in front of it c > 0.9; a wrongly flagged pair
-// costs its test, never the result.  A non-finite sphere: no pair.
-// RT_CAND_MERGE: "all" and "off" leave no forward pair, "fwd-all" makes every
-// pair of the caller's order one.
-void pair_forward(const rt_scene* scene, HostScene& hs)
-{
-    constexpr double kFwdCos = -0.9;
-    SceneFacts& f = hs.facts;
-    const int ns = f.ns;
-    f.ns_fwd = 0;
-    const char* mode = std::getenv("RT_CAND_MERGE");
-    if (mode && (!std::strcmp(mode, "all") || !std::strcmp(mode, "off"))) return;
-    if (mode && !std::strcmp(mode, "fwd-all")) {
-        f.ns_fwd = f.ns_pad - f.ns_merge;        // (order_candidates flagged none: all of them)
-        return;
-    }
-    if (ns < 3 || !std::isfinite(f.cand_lmax)) return;
-    for (int i = 0; i < ns; ++i) {
-        const rt_sphere& s = scene->sphere_list[i];
-        if (!(std::isfinite(s.radius) && std::isfinite(s.center.e[0]) && std::isfinite(s.center.e[1]) &&
-              std::isfinite(s.center.e[2])))
-            return;
-    }
-    auto rad = [&](int i) { return std::fabs(scene->sphere_list[i].radius); };
-    std::vector<int> big;                        // the unflagged spheres (not the padding record)
-    for (int j = f.ns_merge; j < f.ns_pad; ++j)
-        if (hs.cand_orig[j] < ns) big.push_back(hs.cand_orig[j]);
-    const int m = std::min((int)big.size(), kMergeScan);
-    std::partial_sort(big.begin(), big.begin() + m, big.end(),
-                      [&](int x, int y) { return rad(x) != rad(y) ? rad(x) > rad(y) : x < y; });
-    long double sum[3] = {0.0L, 0.0L, 0.0L};
-    for (int i = 0; i < ns; ++i)
-        for (int a = 0; a < 3; ++a) sum[a] += scene->sphere_list[i].center.e[a];
-    std::vector<char> used((size_t)ns, 0);
-    std::vector<int> front;
-    for (int ii = 0; ii < m; ++ii) {
-        const int i = big[ii];
-        if (used[i]) continue;
-        int best = -1;
-        double cbest = HUGE_VAL;
-        for (int jj = ii + 1; jj < m; ++jj) {
-            const int j = big[jj];
-            if (used[j]) continue;
-            const rt_sphere &p = scene->sphere_list[i], &q = scene->sphere_list[j];
-            double d2 = 0.0, uv = 0.0, uu = 0.0, vv = 0.0;
-            for (int a = 0; a < 3; ++a) {
-                const double P = (double)((sum[a] - p.center.e[a] - q.center.e[a]) / (ns - 2));
-                const double u = p.center.e[a] - P, v = q.center.e[a] - P;
-                d2 += (p.center.e[a] - q.center.e[a]) * (p.center.e[a] - q.center.e[a]);
-                uv += u * v;
-                uu += u * u;
-                vv += v * v;
-            }
-            const double rs = rad(i) + rad(j);
-            if (!(d2 > rs * rs * (1.0 + 0x1p-12)) || !(uu > rad(i) * rad(i)) || !(vv > rad(j) * rad(j))) continue;
-            const double c = uv / std::sqrt(uu * vv);           // (overflow: NaN, never the smallest)
-            if (c < cbest) {
-                cbest = c;
-                best = j;
-            }
-        }
-        if (best >= 0 && cbest <= kFwdCos) {
-            used[i] = used[best] = 1;
-            front.push_back(i);
-            front.push_back(best);
-        }
-    }
-    if (front.empty()) return;
-    // the unflagged records again: the pairs, then the others as they were
-    std::vector<int> slot_of((size_t)f.ns_pad, -1), order(front);
-    for (int j = f.ns_merge; j < f.ns_pad; ++j) {
-        slot_of[(size_t)hs.cand_orig[j]] = j;
-        if (hs.cand_orig[j] >= ns || !used[hs.cand_orig[j]]) order.push_back(hs.cand_orig[j]);
-    }
-    const std::vector<SphCand> cand(hs.sph_cand);
-    const std::vector<SphGeo> slot(hs.sph_slot);
-    for (size_t k = 0; k < order.size(); ++k) {
-        const size_t to = (size_t)f.ns_merge + k, from = (size_t)slot_of[(size_t)order[k]];
-        hs.cand_orig[to] = order[k];
-        hs.sph_cand[to] = cand[from];
-        hs.sph_slot[to] = slot[from];
-    }
-    f.ns_fwd = (int)front.size();
 }
 
 }  // namespace rt

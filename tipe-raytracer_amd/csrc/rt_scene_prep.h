@@ -42,7 +42,7 @@ struct SceneFacts {
 template <template <class> class Array>
 struct SceneArrays {
     Array<SphGeo> sph;               // [ns_pad], the caller's order
-    Array<SphCand> sph_cand;         // [ns_pad], candidate-record order (order_candidates, pair_forward)
+    Array<SphCand> sph_cand;         // [ns_pad], candidate-record order (rt_scene_prep.cpp pair_candidates)
     Array<int> cand_orig;            // the sphere index of each candidate record
     Array<SphGeo> sph_slot;          // sph in candidate-record order
     Array<DevMat> sph_mat;
@@ -68,8 +68,5 @@ struct HostScene : SceneArrays<HostArray> {
 // Fills `out` from a scene that passed validation.  RT_OK, or RT_EUNSUPPORTED
 // with `err` set (2^31 texels or more; mat_list is then not read).
 int prepare_scene(const rt_scene* scene, HostScene& out, std::string& err);
-// Chooses the forward pairs of a prepared scene and moves their candidate
-// records behind the flagged ones (facts.ns_fwd; rt_scene_prep.cpp).  Host only.
-void pair_forward(const rt_scene* scene, HostScene& hs);
 
 }  // namespace rt

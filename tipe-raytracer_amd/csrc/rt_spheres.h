@@ -73,33 +73,13 @@ __device__ __forceinline__ int spheres_exact_scan(const KParams& kp, const V3 o,
     return win;
 }
 
-// Closest sphere (main.c:59-78): an FMA candidate pass with rigorous error
-// intervals picks the winner, whose exact reference test then runs alone;
-// any ambiguity reruns the exact scan for that ray (DESIGN.md "Exact closest
-// hit").  Half-b form: h = (o-C).d, D = h^2 - a*c, roots n1,2 = -h -/+ sqrt(D)
-// with t = n/a (the reference's t1,2 = (-b -/+ sqrt(disc))/(2a) scale
-// exactly: b = 2h, disc = 4D).  Intervals are kept in n = a*t units, one
-// per-ray half-width M for every sphere:
-//   h  = od - C.d                       (3 fma; od = o.d per ray)
-//   ca = a|o|^2 - 2a o.C + a*k          (4 fma; k = |C|^2 - r2 from the host)
-//   D  = fma(h, h, -ca)
-// Error bound (DESIGN.md): with Hs >= (|o| + L) sqrt(a), L >= |C_k| + R_k,
-// |D - D_ref| <= 52.5u*Hs^2 <= 2^-47.3 Hs^2 (u = 2^-53), where D_ref =
-// disc_ref/4.  Rays with D >= T1 = 2^-36 Hs^2 are resolved: the reference's
-// disc > 0, and sa (v_rsq_f64 + one Newton step, <= 2^-45 relative) is within
-// 2^-29.3 Hs of its rounded sqrt, so |n - n_ref| <= 2^-29.29 Hs; a*t_ref lies
-// within u|n| of n_ref.  M = 2^-26 Hs (+ thr*2^-48 for the rounding of
-// thr = a*1e-4) leaves a factor 9.8 of slack.  D < -T2 = -2^-44 Hs^2 is a sure
-// miss; in between (grazing rays) the ray is ambiguous.  Root choice follows
-// hit_sphere: n1 if it may reach 1e-4 (a straddle is ambiguous), else n2.
-// Two winners closer than 2M are ambiguous, so a strictly smaller interval is
-// a strictly smaller t_ref (the reference keeps the first of equal t).
-// Non-finite o, d or Hs^2 > 2^1000 make the ray ambiguous up front.
-// CU (main_cuda.cu's thresholds): t1 >= 0, t2 >= 0.001, one interval pair each.
+// ---- The pieces of the sphere candidate pass (spheres_closest, below) ----
+
 // The candidate's n with its low 16 mantissa bits replaced by sphere slot k:
 // one v_and_or_b32 with the mask in a VGPR (msk, loop-invariant; a literal
 // would split it into v_and + v_or) and the wave-uniform slot as its one
-// scalar operand.
+// scalar operand.  Host: ns_cand <= 65534; |nt - n| < 2^-36 |n| <= 2^-34.4 Hs,
+// inside M's slack.
 __device__ __forceinline__ double cand_tag(double n, int k, uint32_t msk)
 {
     uint32_t lo;
@@ -153,10 +133,13 @@ __device__ __forceinline__ bool any_above_half(V3 r)
     return dmax_raw(dmax_raw(r.x, r.y), r.z) > 0.5;
 }
 
+// tools/merge_share.py (RT_DIAG_MERGE builds): the per-wave counters of the pair
+// loops' wave-casts that ran one root tail or two; render_kernel_q (rt_queue.h)
+// clears them and writes them into its trace record.
+enum DiagMerge { DM_FLAGGED_ONE = 0, DM_FLAGGED_TWO = 4, DM_FORWARD_ONE = 8, DM_FORWARD_TWO = 12 };
 #if RT_DIAG_MERGE
-// tools/merge_share.py: flagged pairs that took one tail [0] / two tails [4],
-// forward pairs likewise [8] / [12], per wave of the block (every active lane
-// adds the same wave-uniform step)
+// one counter per wave of the block (every active lane adds the same
+// wave-uniform step)
 __device__ __forceinline__ unsigned* diag_merge()
 {
     __shared__ unsigned dm_lds[16];
@@ -164,33 +147,124 @@ __device__ __forceinline__ unsigned* diag_merge()
 }
 #endif
 
-// (MN) The root tail of one sphere of the candidate scan: its tagged
-// candidate from h and D, or a sentinel above 2^1000 that keeps the tag.
+// A sphere that is no candidate enters the two minima as a sentinel: finite,
+// above 2^1000 (this high word), its low word the tag it would have had.  The
+// decisions after the scan only ask whether a minimum is a sentinel, which is
+// whether it is above kCandNone (every candidate's n is below: Hs^2 <= 2^1000).
+constexpr int kSentinelHi = 0x7fefffff;
+constexpr double kCandNone = 0x1p600;
+
+// What one ray's scan keeps per sphere record g = {C, k} (k = |C|^2 - r2 from
+// the host), in the half-b form of spheres_closest's header:
+//   h  = od - C.d                       (3 fma; od = o.d per ray)
+//   ca = a|o|^2 - 2a o.C + a*k          (4 fma)
+// and D = fma(h, h, -ca); thrM and msk are what a root tail reads.
+struct CandRay {
+    V3 d;
+    double od, a, aoo, oax, oay, oaz;    // o.d, |d|^2, a|o|^2, -2a o
+    double thrM;                         // thr1 - M: a root at or above it may reach the threshold
+    uint32_t msk;                        // cand_tag's mask
+    __device__ __forceinline__ double h(const double* g) const
+    {
+        return fma(-g[2], d.z, fma(-g[1], d.y, fma(-g[0], d.x, od)));
+    }
+    __device__ __forceinline__ double ca(const double* g) const
+    {
+        return fma(g[2], oaz, fma(g[1], oay, fma(g[0], oax, fma(a, g[3], aoo))));
+    }
+};
+
+// The root of one sphere from h and D, chosen as hit_sphere chooses: n1 if it
+// may reach the threshold (r1), else n2.
 template <bool AMGM>
-__device__ __forceinline__ double cand_tail(double h, double D, double thrM, int k, uint32_t msk)
+__device__ __forceinline__ double cand_root(double h, double D, double thrM, bool& r1)
 {
     // sa ~ sqrt(D): v_rsq_f64 + one Newton step (sa = t + t*e/2)
     const double r0 = __builtin_amdgcn_rsq(D);
     const double tt = D * r0;
     const double sa = fma(tt * 0.5, fma(-tt, r0, 1.0), tt);
     const double n1 = -h - sa;
-    const bool r1 = n1 >= thrM;                     // n1 may reach 1e-4: hit_sphere takes t1
+    r1 = n1 >= thrM;                                // n1 may reach 1e-4: hit_sphere takes t1
     // the chosen root: n1 = -h - sa, or n2 = -h + sa; in the sphere-scene queue
     // kernel (AMGM) as one fma with a selected sign (s * sa is exact; C2
     // +0.7 %), elsewhere a select (the fma's constants cost the BVH
     // instantiations registers: sweep -1.4 %)
-    const double n = AMGM ? fma(r1 ? -1.0 : 1.0, sa, -h) : (r1 ? n1 : sa - h);
-    // candidates: every chosen root that may reach 1e-4 (n >= thr - M),
-    // straddling ones included -- they are below any sure root, so
-    // the winner's own test after the scan (bn < thrP) catches them.
-    // n with its low 16 mantissa bits replaced by the slot (one
-    // v_and_or_b32; host: ns_cand <= 65534); |nt - n| < 2^-36 |n|
-    // <= 2^-34.4 Hs, inside M's slack
-    const double nt = cand_tag(n, k, msk);
-    return __hiloint2double(n >= thrM ? __double2hiint(nt) : 0x7fefffff, __double2loint(nt));
+    return AMGM ? fma(r1 ? -1.0 : 1.0, sa, -h) : (r1 ? n1 : sa - h);
 }
 
-// MG: the flagged-pair loop is compiled in (every kernel whose cast is not
+// (MN) The root tail of one sphere of the candidate scan: its tagged
+// candidate from h and D, or the sentinel with that tag.
+// Candidates: every chosen root that may reach 1e-4 (n >= thr - M),
+// straddling ones included -- they are below any sure root, so the winner's
+// own test after the scan (bn < thrP) catches them.
+// A sphere with !(D > 0) gives the sentinel: rsq of a non-positive D is NaN or
+// inf, D * r0 and with it n is NaN, and n >= thrM fails.
+template <bool AMGM>
+__device__ __forceinline__ double cand_tail(const CandRay& r, double h, double D, int k)
+{
+    bool r1;
+    const double n = cand_root<AMGM>(h, D, r.thrM, r1);
+    const double nt = cand_tag(n, k, r.msk);
+    return __hiloint2double(n >= r.thrM ? __double2hiint(nt) : kSentinelHi, __double2loint(nt));
+}
+
+// (MN) bn and bn2 stay the smallest and the second-smallest tagged candidate
+// with nc among them.
+__device__ __forceinline__ void cand_keep(double& bn, double& bn2, double nc)
+{
+    bn2 = dmin_raw(bn2, dmax_raw(bn, nc));
+    bn = dmin_raw(bn, nc);
+}
+// ... in their own registers (dmin_acc): the update on one side of a branch
+__device__ __forceinline__ void cand_keep_acc(double& bn, double& bn2, double nb)
+{
+    dmin_acc(bn2, dmax_raw(bn, nb));
+    dmin_acc(bn, nb);
+}
+
+// A pair's second tail, sphere k + 1's, which runs only when the wave does not
+// merge: updating bn and bn2 in place, so nothing has two definitions that
+// meet at the latch (a v_mov_b64 each).
+template <bool AMGM>
+__device__ __forceinline__ void cand_second_tail(const CandRay& r, double h1, double D1, int k, double& bn,
+                                                 double& bn2)
+{
+    cand_keep_acc(bn, bn2, cand_tail<AMGM>(r, h1, D1, k + 1));
+}
+
+// Closest sphere (main.c:59-78): an FMA candidate pass with rigorous error
+// intervals picks the winner, whose exact reference test then runs alone;
+// any ambiguity reruns the exact scan for that ray (DESIGN.md "Exact closest
+// hit").  Half-b form: h = (o-C).d, D = h^2 - a*c, roots n1,2 = -h -/+ sqrt(D)
+// with t = n/a (the reference's t1,2 = (-b -/+ sqrt(disc))/(2a) scale
+// exactly: b = 2h, disc = 4D).  Intervals are kept in n = a*t units, one
+// per-ray half-width M for every sphere (CandRay: h, ca and D per record).
+// Error bound (DESIGN.md): with Hs >= (|o| + L) sqrt(a), L >= |C_k| + R_k,
+// |D - D_ref| <= 52.5u*Hs^2 <= 2^-47.3 Hs^2 (u = 2^-53), where D_ref =
+// disc_ref/4.  Rays with D >= T1 = 2^-36 Hs^2 are resolved: the reference's
+// disc > 0, and sa (v_rsq_f64 + one Newton step, <= 2^-45 relative) is within
+// 2^-29.3 Hs of its rounded sqrt, so |n - n_ref| <= 2^-29.29 Hs; a*t_ref lies
+// within u|n| of n_ref.  M = 2^-26 Hs (+ thr*2^-48 for the rounding of
+// thr = a*1e-4) leaves a factor 9.8 of slack.  D < -T2 = -2^-44 Hs^2 is a sure
+// miss; in between (grazing rays) the ray is ambiguous.  Root choice follows
+// hit_sphere: n1 if it may reach 1e-4 (a straddle is ambiguous), else n2.
+// Two winners closer than 2M are ambiguous, so a strictly smaller interval is
+// a strictly smaller t_ref (the reference keeps the first of equal t).
+// Non-finite o, d or Hs^2 > 2^1000 make the ray ambiguous up front.
+// CU (main_cuda.cu's thresholds): t1 >= 0, t2 >= 0.001, one interval pair each.
+//
+// The pass: the per-ray set-up; the scan over the records, which are in the
+// host's order (rt_scene_prep.cpp pair_candidates) -- the first ns_merge are
+// flagged pairs, the next ns_fwd forward pairs, each with a loop that shares
+// one root tail per pair where its rule allows, the rest take the plain loop;
+// one decision after the scan.  The tag is the record's slot, and kp.sph_slot /
+// kp.cand_orig give the winner's sphere.  The order and the two counts are a
+// hint: every order and every ns_merge and ns_fwd give the same winner
+// (tests/test_gpu_merged_tail.py, tests/test_gpu_forward_pairs.py, RT_CAND_MERGE).
+// MN (every instantiation but CUDA semantics): the scan keeps the smallest and
+// second-smallest tagged candidate (bn, bn2; cand_keep) and the smallest |D|
+// (gmin), and ambiguity is decided once after the scan.
+// MG: the pair loops are compiled in (every kernel whose cast is not
 // followed by a BVH walk, and rt_verify_sphere_pass; the BVH instantiations
 // keep the plain loop, which is right for any ns_merge -- with the flagged
 // loop their register allocation lost 0.7 % on C4)
@@ -226,46 +300,35 @@ __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, co
     bool amb = !(fast && Hs2 <= 0x1p1000);
     uint32_t msk = 0xffff0000u;
     asm volatile("" : "+v"(msk));
-    // MN (every instantiation but CUDA semantics): the smallest and
-    // second-smallest tagged candidate (bn, bn2; non-candidates enter as a
-    // finite sentinel above 2^1000 that keeps the tag), ambiguity decided once
-    // after the scan (bn2 - bn <= 2M)
+    const CandRay r{d, od, a, aoo, oax, oay, oaz, thrM, msk};
     constexpr bool MN = !CU;
-    double bn2 = __hiloint2double(0x7fefffff, -1);
+    double bn2 = __hiloint2double(kSentinelHi, -1);
     if (MN) bn = bn2;
     double gmin = bn2;                   // (MN) min |D| over the scan
-    // The records are in the host's order (rt_scene_prep.cpp order_candidates): the
-    // tag is the record's slot, and kp.sph_slot / kp.cand_orig give the
-    // winner's sphere.  The first ns_merge records are flagged pairs: spheres
-    // that a line rarely crosses both of, which share one root tail.
-    // A sphere with !(D > 0) only adds a sentinel: rsq of a non-positive D is
-    // NaN or inf, D * r0 and with it n is NaN, and n >= thrM fails.  Leaving
-    // that update out changes only the low bits of a sentinel in bn or bn2, and
-    // the decisions after the scan (any, bn2 - bn > M2, bk) only ask whether
-    // those are above 2^600; gmin takes both D either way.  So when no lane of
-    // the wave has both D > 0, one tail on each lane's own positive sphere (the
-    // first when neither is) gives what the two tails give; otherwise the two
-    // tails run.  The sign test reads D's high word: a positive D below 2^-1042
-    // counts as not positive, and is below T1 (>= 2^-177 on a fast ray: Hs >=
-    // 2^-20 sqrt(a), a >= 2^-101), where gmin makes the ray ambiguous.  The
-    // order and the flags are a hint: every order and every ns_merge give the
-    // same winner (tests/test_gpu_merged_tail.py, RT_CAND_MERGE).
-    // The flagged loop runs the first tail on each lane's choice (sphere 0
-    // unless the wave merges and the lane's D1 > 0; the choice goes into the
-    // tag's low bit, k being even) and the second tail only when the wave does
-    // not merge, updating bn and bn2 in place, so nothing has two definitions
-    // that meet at the latch (a v_mov_b64 each).  C2: 96 % of the flagged
-    // pairs' wave-casts merge, +1.6 % (profiles/r07_merge/).
     int k = 0;
     if (MN && MG) {
+        // Flagged pairs: spheres that a line rarely crosses both of.  A sphere
+        // with !(D > 0) only adds a sentinel (cand_tail).  Leaving that update
+        // out changes only the low bits of a sentinel in bn or bn2, which the
+        // decisions after the scan (any, bn2 - bn > M2, bk) do not read
+        // (kCandNone); gmin takes both D either way.  So when no lane of the wave
+        // has both D > 0, one tail on each lane's own positive sphere (the
+        // first when neither is) gives what the two tails give; otherwise the two
+        // tails run.  The sign test reads D's high word: a positive D below 2^-1042
+        // counts as not positive, and is below T1 (>= 2^-177 on a fast ray: Hs >=
+        // 2^-20 sqrt(a), a >= 2^-101), where gmin makes the ray ambiguous.
+        // The first tail runs on each lane's choice (sphere 0 unless the wave
+        // merges and the lane's D1 > 0) and the second only when the wave does
+        // not merge.  C2: 96 % of the flagged pairs' wave-casts merge, +1.6 %
+        // (profiles/r07_merge/).
         for (; k < kp.ns_merge; k += 2) {
             double g[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) g[j] = sc[4 * k + j];
-            const double h0 = fma(-g[2], d.z, fma(-g[1], d.y, fma(-g[0], d.x, od)));
-            const double D0 = fma(h0, h0, -fma(g[2], oaz, fma(g[1], oay, fma(g[0], oax, fma(a, g[3], aoo)))));
-            double h1 = fma(-g[6], d.z, fma(-g[5], d.y, fma(-g[4], d.x, od)));
-            double D1 = fma(h1, h1, -fma(g[6], oaz, fma(g[5], oay, fma(g[4], oax, fma(a, g[7], aoo)))));
+            const double h0 = r.h(g);
+            const double D0 = fma(h0, h0, -r.ca(g));
+            double h1 = r.h(g + 4);
+            double D1 = fma(h1, h1, -r.ca(g + 4));
             // (opaque to the compiler: paired up as two-element vectors, the two
             // spheres cost a copy of every loop-invariant operand per cast)
             asm("" : "+v"(h1), "+v"(D1));
@@ -273,32 +336,27 @@ __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, co
             const int s0 = __double2hiint(D0), s1 = __double2hiint(D1);
             const bool merged = __builtin_amdgcn_ballot_w64(min(s0, s1) > 0) == 0;
 #if RT_DIAG_MERGE
-            diag_merge()[merged ? 0 : 4] += 1u;
+            diag_merge()[merged ? DM_FLAGGED_ONE : DM_FLAGGED_TWO] += 1u;
 #endif
             const bool sel = merged && s1 > 0;
-            double nc = cand_tail<AMGM>(sel ? h1 : h0, sel ? D1 : D0, thrM, k, msk);
+            double nc = cand_tail<AMGM>(r, sel ? h1 : h0, sel ? D1 : D0, k);
+            // the lane's choice into the tag's low bit (k is even)
             nc = __hiloint2double(__double2hiint(nc), __double2loint(nc) + (sel ? 1 : 0));
-            bn2 = dmin_raw(bn2, dmax_raw(bn, nc));
-            bn = dmin_raw(bn, nc);
-            if (!merged) {
-                const double nb = cand_tail<AMGM>(h1, D1, thrM, k + 1, msk);
-                dmin_acc(bn2, dmax_raw(bn, nb));
-                dmin_acc(bn, nb);
-            }
+            cand_keep(bn, bn2, nc);
+            if (!merged) cand_second_tail<AMGM>(r, h1, D1, k, bn, bn2);
         }
-        // Forward pairs, records [ns_merge, ns_merge + ns_fwd): two spheres that a
-        // ray starting between them moves towards at most one of (the README
+        // Forward pairs: two spheres that a ray starting
+        // between them moves towards at most one of (the README
         // box's opposite walls: D > 0 for both on almost every ray, so the test
         // above never merges them).  A lane's sphere is dead when
         //   h > hmin  and  ca > -cmin        (the computed h and ca of this scan)
         // and live otherwise, whatever its D; the wave merges when no lane is
         // live for both, and the one tail runs on the lane's live sphere (sphere
-        // 0 when neither is; the choice goes into the tag's low bit).  With hmin =
-        // 2^-16 Hs and cmin = 2^-44 Hs^2, and on rays with thrM >= 2^-26 Hs only
+        // 0 when neither is).  With hmin = 2^-16 Hs and cmin = 2^-44 Hs^2, and on rays with thrM >= 2^-26 Hs only
         // (else hthr lets no lane certify; that covers thrM < 0), a dead
         // sphere's tail only writes a sentinel: D =
-        // fl(h^2 - ca) <= (h^2 + cmin)(1 + u); D <= 0 or NaN gives the sentinel as
-        // above; else sa <= sqrt(D)(1 + 2^-45) <= (h + cmin / 2h)(1 + 2^-44), and
+        // fl(h^2 - ca) <= (h^2 + cmin)(1 + u); D <= 0 or NaN gives the sentinel
+        // (cand_tail); else sa <= sqrt(D)(1 + 2^-45) <= (h + cmin / 2h)(1 + 2^-44), and
         // with hmin < h <= 1.01 Hs
         //   n1 = -h - sa < -hmin < 0 < thrM                  (r1 is false: n = n2)
         //   n2 = fl(sa - h) <= cmin / 2hmin + 2^-43 Hs = (2^-29 + 2^-43) Hs,
@@ -336,11 +394,9 @@ __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, co
             double g[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) g[j] = sc[4 * k + j];
-            const double h0 = fma(-g[2], d.z, fma(-g[1], d.y, fma(-g[0], d.x, od)));
-            const double ca0 = fma(g[2], oaz, fma(g[1], oay, fma(g[0], oax, fma(a, g[3], aoo))));
-            double h1 = fma(-g[6], d.z, fma(-g[5], d.y, fma(-g[4], d.x, od)));
-            double ca1 = fma(g[6], oaz, fma(g[5], oay, fma(g[4], oax, fma(a, g[7], aoo))));
-            asm("" : "+v"(h1), "+v"(ca1));
+            const double h0 = r.h(g), ca0 = r.ca(g);
+            double h1 = r.h(g + 4), ca1 = r.ca(g + 4);
+            asm("" : "+v"(h1), "+v"(ca1));               // (as in the flagged loop)
             // (a ballot per comparison: one ballot of the combined predicate goes
             // through a v_cndmask and a v_cmp_ne)
             const bool lh0 = __double2hiint(h0) <= hthr, lc0 = (uint32_t)__double2hiint(ca0) >= cthr;
@@ -348,30 +404,27 @@ __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, co
             const uint64_t l1 = __builtin_amdgcn_ballot_w64(lh1) | __builtin_amdgcn_ballot_w64(lc1);
             const bool merged = ((__builtin_amdgcn_ballot_w64(lh0) | __builtin_amdgcn_ballot_w64(lc0)) & l1) == 0;
 #if RT_DIAG_MERGE
-            diag_merge()[merged ? 8 : 12] += 1u;
+            diag_merge()[merged ? DM_FORWARD_ONE : DM_FORWARD_TWO] += 1u;
 #endif
             const bool sel = merged && (lh1 || lc1);
-            // D and the grazing test of the chosen sphere only: the reference
-            // itself misses a dead sphere (above), grazing or not
+            // D and the grazing test of the chosen sphere only
             const double hs = sel ? h1 : h0, cas = sel ? ca1 : ca0;
             const double Ds = fma(hs, hs, -cas);
             dmin_abs_acc(gmin, Ds);
-            double nc = cand_tail<AMGM>(hs, Ds, thrM, k, msk);
-            // the choice into the tag's low bit, as the carry-in of one add
+            double nc = cand_tail<AMGM>(r, hs, Ds, k);
+            // the choice into the tag's low bit, here as the carry-in of one add
+            // (the wave's mask of such lanes is there already)
             uint32_t lo;
             asm("v_addc_co_u32_e64 %0, vcc, 0, %1, %2"
                 : "=v"(lo)
                 : "v"((uint32_t)__double2loint(nc)), "s"(merged ? l1 : (uint64_t)0)
                 : "vcc");
             nc = __hiloint2double(__double2hiint(nc), (int)lo);
-            bn2 = dmin_raw(bn2, dmax_raw(bn, nc));
-            bn = dmin_raw(bn, nc);
+            cand_keep(bn, bn2, nc);
             if (!merged) {
                 const double D1 = fma(h1, h1, -ca1);
                 dmin_abs_acc(gmin, D1);
-                const double nb = cand_tail<AMGM>(h1, D1, thrM, k + 1, msk);
-                dmin_acc(bn2, dmax_raw(bn, nb));
-                dmin_acc(bn, nb);
+                cand_second_tail<AMGM>(r, h1, D1, k, bn, bn2);
             }
         }
     }
@@ -381,49 +434,41 @@ __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, co
         for (int j = 0; j < 8; ++j) g[j] = sc[4 * k + j];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            const double cx = g[4 * e], cy = g[4 * e + 1], cz = g[4 * e + 2], kk = g[4 * e + 3];
-            const double h = fma(-cz, d.z, fma(-cy, d.y, fma(-cx, d.x, od)));
-            const double ca = fma(cz, oaz, fma(cy, oay, fma(cx, oax, fma(a, kk, aoo))));
-            const double D = fma(h, h, -ca);
-            // D finite here.  The ambiguity tests use xor of nested conditions
-            // (a implies b: b && !a == a ^ b) so each comparison is issued once.
+            const double h = r.h(g + 4 * e);
+            const double D = fma(h, h, -r.ca(g + 4 * e));
+            // D finite here.
             // MN: one |D| < T1 test (grazing band widened from [-T2, T1) to
-            // (-T1, T1)); D <= -T1 gives a NaN root in cand_tail, which no
-            // comparison accepts, so `valid` is implied by the candidate test
+            // (-T1, T1)), once, after the scan; D <= -T1 gives a NaN root in
+            // cand_tail, which no comparison accepts, so `valid` is implied by
+            // the candidate test
             if (MN) {
-                gmin = dmin_abs2(gmin, D);                  // grazing test once, after the scan
-                const double nc = cand_tail<AMGM>(h, D, thrM, k + e, msk);
-                bn2 = dmin_raw(bn2, dmax_raw(bn, nc));
-                bn = dmin_raw(bn, nc);
-                continue;
+                gmin = dmin_abs2(gmin, D);
+                cand_keep(bn, bn2, cand_tail<AMGM>(r, h, D, k + e));
+            } else {
+                // CU: ambiguity is decided sphere by sphere, bn the one running
+                // winner.  The tests use xor of nested conditions (a implies b:
+                // b && !a == a ^ b) so each comparison is issued once.
+                const bool valid = D >= T1;
+                amb = amb || (valid != (D >= nT2));             // -T2 <= D < T1: grazing
+                bool r1;
+                const double n = cand_root<AMGM>(h, D, thrM, r1);
+                const double tP = r1 ? thrP : thrP2, tM = r1 ? thrM : thrM2;
+                const bool sure = n >= tP;
+                amb = amb || (valid && (sure != (n >= tM)));    // the chosen root straddles the threshold
+                const bool cand = valid && sure;
+                const double nt = cand_tag(n, k + e, msk);
+                const double diff = nt - bn;
+                const bool closer = cand && diff < -M2;
+                amb = amb || (cand && fabs(diff) <= M2);        // (closer implies |diff| > M2)
+                bn = closer ? nt : bn;
             }
-            const bool valid = D >= T1;
-            amb = amb || (valid != (D >= nT2));             // -T2 <= D < T1: grazing
-            // sa ~ sqrt(D): v_rsq_f64 + one Newton step (sa = t + t*e/2)
-            const double r0 = __builtin_amdgcn_rsq(D);
-            const double tt = D * r0;
-            const double sa = fma(tt * 0.5, fma(-tt, r0, 1.0), tt);
-            const double n1 = -h - sa;
-            const bool r1 = n1 >= thrM;                     // n1 may reach 1e-4: hit_sphere takes t1
-            // the chosen root: n1 = -h - sa, or n2 = -h + sa (cand_tail)
-            const double n = AMGM ? fma(r1 ? -1.0 : 1.0, sa, -h) : (r1 ? n1 : sa - h);
-            const double tP = r1 ? thrP : thrP2, tM = r1 ? thrM : thrM2;
-            const bool sure = n >= tP;
-            amb = amb || (valid && (sure != (n >= tM)));    // the chosen root straddles 1e-4
-            const bool cand = valid && sure;
-            // the slot in n's low 16 mantissa bits, as in cand_tail
-            const double nt = cand_tag(n, k + e, msk);
-            const double diff = nt - bn;
-            const bool closer = cand && diff < -M2;
-            amb = amb || (cand && fabs(diff) <= M2);        // (closer implies |diff| > M2)
-            bn = closer ? nt : bn;
         }
     }
     if (MN) {
         // the winner is sure (its tagged value, within 2^-36 |n| of n, clears
         // thr + M with that margin) and every other candidate lies more than
-        // 2M above it; no candidate: bn is the sentinel (> 2^1000)
-        const bool any = bn < 0x1p600;
+        // 2M above it; no candidate: bn is the sentinel
+        const bool any = bn < kCandNone;
         amb = amb || gmin < T1;
         amb = amb || (any && (bn < thrP * (1.0 + 0x1p-34) || !(bn2 - bn > M2)));
         bk = any ? (int)((uint32_t)__double2loint(bn) & 0xffffu) : -1;

@@ -7,7 +7,10 @@
 The diagnostic build counts, per wave, the flagged pairs that took the merged
 form and those that fell back to two tails, and writes both into the wave's
 RT_QUEUE_TRACE record (in place of rounds and tasks), and the same two counts
-of the forward pairs (in place of the two clocks).  One JSON line per scene."""
+of the forward pairs (in place of the two clocks): the four counters are
+rt_spheres.h's DiagMerge slots, and the record's words 2, 3, 0 and 1 are
+DM_FLAGGED_ONE, DM_FLAGGED_TWO, DM_FORWARD_ONE and DM_FORWARD_TWO.  The pairs
+are the host's (rt_scene_prep.cpp pair_candidates).  One JSON line per scene."""
 import json
 import os
 import sys

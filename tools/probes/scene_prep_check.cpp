@@ -2,8 +2,6 @@
 // stdin, prepares it and prints one JSON line with the SceneFacts fields and,
 // per array, its element count, a 64-bit FNV-1a hash of its bytes and (up to
 // argv[1] elements, default 64; never for the BVH nodes) its contents.
-// argv[2] "fwd": pair_forward runs on the prepared scene first, as in
-// rt_scene_upload (tests/test_forward_pairs_host.py).
 // Input, whitespace-separated, numbers as strtod reads them (inf, nan, hex):
 //   spheres N            then N x: cx cy cz radius MAT
 //   triangles N tw th nm then N x: A(3) B(3) C(3) uvA(2) uvB(2) uvC(2) quelMat MAT
@@ -202,7 +200,6 @@ int main(int argc, char** argv)
         std::printf("{\"rc\": %d, \"error\": \"%s\"}\n", rc, err.c_str());
         return 0;
     }
-    if (argc > 2 && !std::strcmp(argv[2], "fwd")) pair_forward(&sc, hs);
     const SceneFacts& f = hs.facts;
     std::printf("{\"rc\": 0, ");
     fact("ns", f.ns);
