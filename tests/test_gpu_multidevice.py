@@ -39,7 +39,11 @@ def _slots(n):
 
 @pytest.mark.parametrize("slots,tile_rows,chunks,scene", [(2, 1, 4, "pyramid"), (3, 4, 1, "pyramid"),
                                                           (2, 2, 1, "pyramid"), (2, 1, 4, "tree"),
-                                                          (3, 1, 32, "tree")])
+                                                          (3, 1, 32, "tree"),
+                                                          # 11 four-row tiles, the last with one row: every
+                                                          # slot has padding rows (queue kernel, table and
+                                                          # register task decode)
+                                                          (3, 4, 4, "pyramid"), (3, 4, 4, "tree")])
 def test_render_gather_slots_bitexact(slots, tile_rows, chunks, scene):
     """tree: the C4 scene (1320-triangle BVH + AO 2.5, 8 bounces) through the
     BVH queue kernel on cyclic 1-row tiles and the gather -- C4's own

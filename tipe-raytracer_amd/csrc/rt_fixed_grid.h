@@ -113,13 +113,15 @@ struct CamDraws {
     }
 };
 
+// The ray before its normalize: the origin no and (returned) dest - no.  st: the
+// sample's draws (Stream, or CamDraws), taken in the order ju, jv, jx, jy; pin
+// (kp.cam_pin: zero aperture, host-checked): the origin is the camera's own and
+// the last two draws are not made.
 template <bool CU, class ST>
-__device__ __forceinline__ void camera_ray(const KParams& kp, int x, int g, ST& st, V3& no, V3& rd)
+__device__ __forceinline__ V3 camera_ray_raw(const KParams& kp, int x, int g, ST& st, bool pin, V3& no)
 {
     const double ju = rand_m05(st.next31());     // randomDouble(-0.5, 0.5)
     const double jv = rand_m05(st.next31());
-    const double jx = rand_m05(st.next31());
-    const double jy = rand_m05(st.next31());
     const int b = opq0();
     const cdptr U = (cdptr)kp.uni;
     // main.c:265-266; main_cuda.cu:152-153 adds 0.5 first
@@ -130,7 +132,6 @@ __device__ __forceinline__ void camera_ray(const KParams& kp, int x, int g, ST& 
     const double rcw = U[b + U_RC_WM1], rch = U[b + U_RC_HM1];
     const double u = rcw != 0.0 ? div_core(nu, U[b + U_WM1], rcw) : nu / U[b + U_WM1];
     const double v = rch != 0.0 ? div_core(nv, U[b + U_HM1], rch) : nv / U[b + U_HM1];
-    const double dx = jx * U[b + U_OX], dy = jy * U[b + U_OY];
     // get_ray, camera.h:42-55
     const V3 co = v3(U[b + U_CAM_O], U[b + U_CAM_O + 1], U[b + U_CAM_O + 2]);
     const V3 ch = v3(U[b + U_CAM_H], U[b + U_CAM_H + 1], U[b + U_CAM_H + 2]);
@@ -138,8 +139,20 @@ __device__ __forceinline__ void camera_ray(const KParams& kp, int x, int g, ST& 
     const V3 cc = v3(U[b + U_CAM_C], U[b + U_CAM_C + 1], U[b + U_CAM_C + 2]);
     const V3 dir = cc + (muls(ch, u) + (muls(cv, v) - co));
     const V3 dest = co + muls(dir, U[b + U_FOCUS]);
-    no = co + v3(dx, dy, 0);
-    rd = normalize(dest - no);
+    if (pin) {
+        no = co;
+    } else {
+        const double jx = rand_m05(st.next31());
+        const double jy = rand_m05(st.next31());
+        const double dx = jx * U[b + U_OX], dy = jy * U[b + U_OY];
+        no = co + v3(dx, dy, 0);
+    }
+    return dest - no;
+}
+template <bool CU, class ST>
+__device__ __forceinline__ void camera_ray(const KParams& kp, int x, int g, ST& st, V3& no, V3& rd)
+{
+    rd = normalize(camera_ray_raw<CU>(kp, x, g, st, false, no));
 }
 
 // Resumable trace for the BVH kernel: the same tracer and
@@ -151,17 +164,17 @@ __device__ __forceinline__ void camera_ray(const KParams& kp, int x, int g, ST& 
 //   SM_TRAV    visits nodes of the triangle BVH,
 // and a lane's casts, draws and sums happen in the same order as in tracer,
 // so results are bit-identical.  samples_coop runs it (the fixed-grid BVH
-// kernel: spp_chunks 1, trees too deep for the queue kernel's stacks); r01's
-// samples_sm (each lane at most 4 node visits per round) is superseded by the
-// queue kernel's resumable walks (render_kernel_q<.., QB>).
+// kernel: spp_chunks 1, trees too deep for the queue kernel's stacks); the
+// queue kernel (render_kernel_q<.., QB>) resumes its walks round by round with
+// the same states.
 enum : int { SM_RESOLVE = 0, SM_CAM = 1, SM_CAST = 2, SM_TRAV = 3, SM_DONE = 4 };
 
-// AOM: AO compiled out (0), always on (1), or read from kp.useAO (2); the
-// queue kernel is instantiated per AO setting so a sphere scene without AO
-// carries neither the AO cast's state nor its code.
-enum : int { AO_OFF = 0, AO_ON = 1, AO_RUNTIME = 2 };
+// QPath's AOM: AO compiled out (0) or always on (1): the queue kernel is
+// instantiated per AO setting so a sphere scene without AO carries neither the
+// AO cast's state nor its code.  LanePath reads kp.useAO.
+enum : int { AO_OFF = 0, AO_ON = 1 };
 
-template <bool COUNT, bool SKY, int AOM = AO_RUNTIME>
+template <bool COUNT, bool SKY>
 struct LanePath {
     Stream st;
     V3 o, d, cd;                                 // ray, next bounce direction, current cast's direction
@@ -209,8 +222,8 @@ struct LanePath {
         bool add_inc = true;                 // false: direct view of a light (tracer returns early)
         st.k0 = kp.key0;                     // the key from the kernel argument (uniform), not
         st.k1 = kp.key1;                     // a loop-carried copy
-        const bool use_ao = AOM == AO_RUNTIME ? kp.useAO != 0 : AOM == AO_ON;
-        if (AOM != AO_OFF && ao_cast) {
+        const bool use_ao = kp.useAO != 0;
+        if (ao_cast) {
             const double AO = ((cdptr)kp.uni)[opq0() + U_AO];
             const double occ = ao_tail(kind != HIT_NONE, o, cd, best, AO);
             rc = mulv(rc, v3(occ, occ, occ));
@@ -277,7 +290,7 @@ struct LanePath {
                     }
                 }
                 if (shade) {
-                    V3 r = rc;
+                    V3 r = rc;                   // (QPath::shade_with, rt_queue.h: the same shading)
                     if (use_ao) {
                         const double AO = ((cdptr)kp.uni)[opq0() + U_AO];
                         const V3 em = muls(mat.emis, mat.es * 1.5 * AO);
@@ -300,7 +313,7 @@ struct LanePath {
                 }
             }
         }
-        if (AOM != AO_OFF && ao_cast) {
+        if (ao_cast) {
             state = SM_CAST;
         } else {
             if (more) {
@@ -353,12 +366,10 @@ struct LanePath {
         }
     }
 
-    // the whole cast in one go (spheres, then brute-force triangles or the
-    // lane's own BVH walk)
-    template <bool BVH = false>
+    // the whole cast in one go (spheres, then brute-force triangles)
     __device__ __forceinline__ void cast_flat(const KParams& kp, Cnt& cnt)
     {
-        kind = closest_hit<COUNT, BVH>(kp, o, cd, best, win, cnt);
+        kind = closest_hit<COUNT, false>(kp, o, cd, best, win, cnt);
         state = SM_RESOLVE;
     }
 
@@ -374,20 +385,13 @@ struct LanePath {
         state = SM_TRAV;
     }
 
-    // up to k node visits; RESOLVE when the traversal is over
+    // one node visit; RESOLVE when the traversal is over
     template <class SE>
-    __device__ __forceinline__ void trav(const KParams& kp, SE* stk, int k, Cnt& cnt)
+    __device__ __forceinline__ void trav(const KParams& kp, SE* stk, Cnt& cnt)
     {
-#pragma unroll 1
-        for (int j = 0; j < k; ++j) {
-            if (!bvh_step<COUNT, false>(kp, o, cd, r32, stk, node, sp, best, kind, win, win_orig, cnt)) {
-                state = SM_RESOLVE;
-                break;
-            }
-        }
+        if (!bvh_step<COUNT, false>(kp, o, cd, r32, stk, node, sp, best, kind, win, win_orig, cnt)) state = SM_RESOLVE;
     }
 };
-
 
 
 // The fixed-grid sphere kernel's sample loop as LanePath rounds: each
@@ -464,80 +468,6 @@ __device__ __forceinline__ void lifo_push(volatile unsigned* q, int& cnt, int n,
     __builtin_amdgcn_wave_barrier();
 }
 
-// One node visit of a cooperative task: as bvh_step, but hit internal
-// children other than the next one go to push[] (for the LIFO) when
-// to_lifo, else on the lane's own stack.  hit: a triangle beat the record.
-template <bool COUNT, class SE>
-__device__ __forceinline__ bool coop_step(const KParams& kp, const V3 o, const V3 d, const Ray32& r32,
-                                          SE* stk, int& node, int& sp, double& best, int& kind,
-                                          int& win, int& win_orig, bool& hit, bool to_lifo, unsigned* push,
-                                          int& npush, Cnt& cnt)
-{
-    const BvhNode4* nd = kp.bvh + node;
-    if (COUNT) {
-        cnt.c[RT_CNT_BVH_NODES] += 1;
-        wave_slots(cnt, RT_CNT_BVH_LANE_SLOTS);
-    }
-    bool h[4];
-    float tn[4];
-    int Ch[4], Cn[4];
-    box4(kp, nd, r32, cull32(kp, best), h, tn, Ch, Cn);
-    int next = -1;
-    float tnext = 0.0f;
-    unsigned lm = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        if (!h[c]) continue;
-        const int ch = nd->child[c], n = nd->count[c];
-        if (n > 0) {
-            lm |= 1u << c;
-        } else if (next < 0) {
-            next = ch;
-            tnext = tn[c];
-        } else {
-            int pu = ch;
-            if (tn[c] < tnext) {
-                pu = next;
-                next = ch;
-                tnext = tn[c];
-            }
-            if (to_lifo) {
-                push[npush] = (unsigned)pu;
-                ++npush;
-            } else {
-                if (COUNT && sp >= kp.stack_cap) cnt.c[RT_CNT_BVH_STACK_OVER] += 1;
-                if (!COUNT || sp < kStack4) {
-                    stk_put(stk, sp, pu);
-                    ++sp;
-                }
-            }
-        }
-    }
-    int k = 0, kend = 0;
-    while (lm != 0u || k < kend) {
-        if (COUNT) wave_slots(cnt, RT_CNT_LEAF_LANE_SLOTS);
-        if (k >= kend) {
-            const int c = __ffs(lm) - 1;
-            lm &= lm - 1u;
-            k = nd->child[c];
-            kend = k + nd->count[c];
-            if (COUNT) cnt.c[RT_CNT_BVH_TRI_TESTS] += (unsigned long long)(kend - k);
-        }
-        const int w0 = win, k0 = kind;
-        tri_test<COUNT, false>(kp, k, o, d, best, kind, win, win_orig);
-        hit = hit || win != w0 || kind != k0;
-        ++k;
-    }
-    if (next >= 0) {
-        node = next;
-        return true;
-    }
-    if (sp == 0) return false;
-    --sp;
-    node = stk_get(stk, sp);
-    return true;
-}
-
 template <bool COUNT, bool SKY, class SE = unsigned short>
 __device__ __forceinline__ void samples_coop(const KParams& kp, int x, int g, uint32_t pixel, int s0, int s1,
                                              uint32_t* rng, double* acc, Cnt& cnt)
@@ -554,7 +484,7 @@ __device__ __forceinline__ void samples_coop(const KParams& kp, int x, int g, ui
         if (L.state == SM_CAM) L.start(kp, x, g, pixel, s1, rng, acc, cnt);
         if (L.state == SM_CAST) {
             L.cast(kp, cnt);
-            L.trav(kp, stk, 1, cnt);             // the root node; SM_TRAV: parked
+            L.trav(kp, stk, cnt);                // the root node; SM_TRAV: parked
         }
         const unsigned long long parked = __ballot(L.state == SM_TRAV);
         const unsigned long long movable = __ballot(L.state == SM_RESOLVE || L.state == SM_CAM);
@@ -612,9 +542,19 @@ __device__ __forceinline__ void samples_coop(const KParams& kp, int x, int g, ui
             int npush = 0;
             const bool to_lifo = qn < 64;
             if (has) {
-                if (!coop_step<COUNT, SE>(kp, to, td, tr32, stk, tnode, tsp, best, kind, win, win_orig, hit, to_lifo,
-                                      push, npush, cnt))
+                // one node visit (bvh_visit, rt_triangles.h): the other hit internal
+                // children go to push[] (for the LIFO) when to_lifo, else on the
+                // lane's own stack.  hit: a triangle beat the record (replacements
+                // are strictly ordered, so it changed iff one did)
+                const int w0 = win, k0 = kind;
+                if (!bvh_visit<COUNT, false, 0, 0, false>(kp, to, td, tr32, stk, tnode, tsp, best, kind, win, win_orig,
+                                                          cnt, nullptr,
+                                                          [&](int pu, float tpu) __attribute__((always_inline)) {
+                                                              if (to_lifo) push[npush++] = (unsigned)pu;
+                                                              else bvh_push<COUNT, false>(kp, stk, tsp, pu, tpu, cnt);
+                                                          }))
                     has = false;
+                hit = win != w0 || kind != k0;
 #pragma unroll
                 for (int j = 0; j < 3; ++j) push[j] = (unsigned)tr | (push[j] << 6);
             }
@@ -651,6 +591,16 @@ __device__ __forceinline__ unsigned udiv_q(unsigned n, unsigned d, unsigned m, u
     return up ? q + 1u : q;
 }
 
+// Global frame row of row yy of the launch's local tile lt (cyclic row tiles:
+// local tile lt is tile tile_first + lt * tile_step of the rows from row_base).
+// A row at or beyond k.row_end is a padding row of the last, partial tile: no work.
+// K: KParams, by value reference or through the queue kernel's KParamsK.
+template <class K>
+__device__ __forceinline__ int tile_row(const K& k, int lt, int yy)
+{
+    return k.row_base + (k.tile_first + lt * k.tile_step) * k.tile_rows + yy;
+}
+
 // First sample of chunk c, rt.h rt_chunk_bound: w(c)*S/den with w(c) = c
 // (den = P) or the tapered weights (den = (P - L) 2^L + 2^L - 1); 32-bit magic
 // division when (den + 1) * S < 2^32 (qm_chunks != 0), else 64-bit.
@@ -685,7 +635,7 @@ __device__ __forceinline__ void render_body(const KParams& kp)
     int g = 0;
     if (valid) {
         const int lt = ly / kp.tile_rows, yy = ly - lt * kp.tile_rows;
-        g = kp.row_base + (kp.tile_first + lt * kp.tile_step) * kp.tile_rows + yy;
+        g = tile_row(kp, lt, yy);
         valid = g < kp.row_end;
     }
     if (valid) {

@@ -8,18 +8,24 @@
 // Semantics follow main.c (the authoritative CPU path), not main_cuda.cu
 // (reference lines -> function, file; this file includes the headers in
 // definition order and keeps the small kernels, launchers and dispatch):
-//   fill_canva        main.c:245-284      -> render_kernel_q (task queue), rt_queue.h /
-//                                            render_kernel (fixed grid), rt_fixed_grid.h;
-//                                            combine_kernel, here
+//   fill_canva        main.c:245-284      -> render_kernel_q (task queue; decode_task is its one
+//                                            task decoder), rt_queue.h / render_kernel (fixed
+//                                            grid; tile_row: local tile row -> frame row),
+//                                            rt_fixed_grid.h; combine_kernel, here
 //   tracer            main.c:118-242      -> QPath (queue kernel), rt_queue.h; LanePath
 //                                            (fixed grid), rt_fixed_grid.h
 //   closest_hit       main.c:52-92        -> closest_hit(), rt_triangles.h
 //   ambient_occlusion main.c:94-116       -> ao_factor() / ao_tail(), rt_shading.h
 //   hit_sphere        sphere.h:13-47      -> sphere_exact() (+ candidate pass), rt_spheres.h
-//   hit_triangle      mesh.h:70-94        -> tri_test(), rt_triangles.h
+//   hit_triangle      mesh.h:70-94        -> tri_test(), rt_triangles.h; the BVH node visit
+//                                            bvh_visit() (bvh_step: a lane's own walk;
+//                                            samples_coop, rt_fixed_grid.h: the wave's)
 //   tri_uvmapping     texture.h:44-90     -> tri_texel(), rt_shading.h
-//   get_ray           camera.h:42-55      -> camera_ray(), rt_fixed_grid.h; render_kernel_q's
-//                                            next-ray step, rt_queue.h
+//   get_ray           camera.h:42-55      -> camera_ray_raw(), rt_fixed_grid.h (camera_ray: its
+//                                            normalize; render_kernel_q's next-ray step shares
+//                                            the bounce lanes' normalize)
+//   shading           main.c:208-234      -> LanePath::resolve, rt_fixed_grid.h;
+//                                            QPath::shade_with, rt_queue.h
 //   random_dir_no_norm / refracted_vec / hsl   rtutility.h:81-231 -> rt_shading.h
 //   write_color_canva rtutility.h:56-71   -> resolve() / write_pixel(), rt_fixed_grid.h
 //   vec3.h                                -> V3, normalize(), rt_vec.h
@@ -156,7 +162,7 @@ __global__ __launch_bounds__(256) void combine_kernel(const KParams kp)
         const int ly = kp.band_y0 + (int)(bi / kp.W);
         const long long li = (long long)kp.band_y0 * kp.W + bi;
         const int lt = ly / kp.tile_rows, yy = ly - lt * kp.tile_rows;
-        const int g = kp.row_base + (kp.tile_first + lt * kp.tile_step) * kp.tile_rows + yy;
+        const int g = tile_row(kp, lt, yy);
         if (g >= kp.row_end) continue;
         double a[9];
         int c0 = 0;
@@ -284,13 +290,14 @@ __global__ __launch_bounds__(256) void denoise_pack_kernel(long long n, const do
     }
 }
 
+// Blocks of 256 threads for n elements of a grid-stride kernel, at most cap.
+static unsigned grid_1d(long long n, long long cap) { return (unsigned)std::min((n + 255) / 256, cap); }
+
 int launch_denoise_pack(long long npx, const double* canva, const double* albedo, const double* normal, float* color3,
                         float* albedo3, float* normal3, void* stream)
 {
     const long long n = npx * 3;
-    long long blocks = (n + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(denoise_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, canva,
+    hipLaunchKernelGGL(denoise_pack_kernel, dim3(grid_1d(n, 8192)), dim3(256), 0, (hipStream_t)stream, n, canva,
                        albedo ? albedo : nullptr, normal, color3, albedo ? albedo3 : nullptr,
                        normal ? normal3 : nullptr);
     return (int)hipGetLastError();
@@ -305,7 +312,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(const KParams kp)
          li += (long long)gridDim.x * blockDim.x) {
         const int ly = (int)(li / kp.W);
         const int lt = ly / kp.tile_rows, yy = ly - lt * kp.tile_rows;
-        const int g = kp.row_base + (kp.tile_first + lt * kp.tile_step) * kp.tile_rows + yy;
+        const int g = tile_row(kp, lt, yy);
         if (g >= kp.row_end) continue;
         const double* a = kp.sums + li * 9;
         write_pixel(kp, li, v3(a[0], a[1], a[2]), v3(a[3], a[4], a[5]), v3(a[6], a[7], a[8]));
@@ -315,10 +322,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(const KParams kp)
 int launch_resolve(const KParams& kp, void* stream)
 {
     const long long npx = (long long)kp.local_rows * kp.W;
-    long long blocks = (npx + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, kp);
+    hipLaunchKernelGGL(resolve_kernel, dim3(std::max(1u, grid_1d(npx, 8192))), dim3(256), 0, (hipStream_t)stream, kp);
     return (int)hipGetLastError();
 }
 
@@ -511,9 +515,7 @@ int launch_render(const KParams& kp, void* stream)
     }
     if (kp.chunks > 1) {
         const long long npx = (long long)kp.band_rows * kp.W;
-        long long blocks = (npx + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(combine_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, kp);
+        hipLaunchKernelGGL(combine_kernel, dim3(grid_1d(npx, 8192)), dim3(256), 0, (hipStream_t)stream, kp);
     }
     return (int)hipGetLastError();
 }
@@ -528,9 +530,7 @@ int launch_assemble(const double* gathered, long long rank_stride, int world, in
                     int H, double* out, void* stream)
 {
     const long long n = (long long)W * H * 3;
-    long long blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, gathered,
+    hipLaunchKernelGGL(assemble_kernel, dim3(grid_1d(n, 4096)), dim3(256), 0, (hipStream_t)stream, gathered,
                        rank_stride, world, tile_rows, rows_per_rank, W, H, out);
     return (int)hipGetLastError();
 }

@@ -293,15 +293,11 @@ struct QPath {
     // shading of an opaque surface (main.c:208-234 without the AO cast)
     __device__ __forceinline__ V3 shade_with(const KParams& kp, V3 emis, double es, V3 diff)
     {
+        // (LanePath::resolve, rt_fixed_grid.h, has the same arithmetic in its two AO branches)
         V3 r = rc_get();
-        if (AOM == AO_ON) {
-            const double AO = ((cdptr)kp.uni)[opq0() + U_AO];
-            const V3 em = muls(emis, es * 1.5 * AO);
-            inc_set(inc_get() + mulv(em, r));
-        } else {
-            const V3 em = muls(emis, es);
-            inc_set(inc_get() + mulv(em, r));
-        }
+        if (AOM == AO_ON) es = es * 1.5 * ((cdptr)kp.uni)[opq0() + U_AO];
+        const V3 em = muls(emis, es);
+        inc_set(inc_get() + mulv(em, r));
         if (any_above_half(r)) r = mulv(diff, muls(r, 1.3));
         const V3 nrc = mulv(diff, r);
         rc_set(nrc);
@@ -379,7 +375,7 @@ __device__ __forceinline__ void decode_task(KParamsK K, unsigned t, uint32_t e[k
     if (ly >= K->local_rows) return;
     unsigned yy;
     const int lt = (int)udiv_q((unsigned)ly, (unsigned)K->tile_rows, K->qm_tile, yy);
-    const int g = K->row_base + (K->tile_first + lt * K->tile_step) * K->tile_rows + (int)yy;
+    const int g = tile_row(*K, lt, (int)yy);
     if (g >= K->row_end) return;
     e[1] = (uint32_t)g * (uint32_t)K->W + xr;
     e[2] = (uint32_t)g;
@@ -424,13 +420,12 @@ void render_kernel_q(const KParams kp)
 #endif
     int x = 0, g = 0, s1 = 0;
     int node = 0, sp = 0, win_orig = 0;      // BVH walk in flight (state SM_TRAV)
-    unsigned chunk = 0, p = 0, pixel = 0;
-    bool owns = false;               // the lane's LDS sums belong to task (chunk, p)
-    // every instantiation but the deep-tree one (QB 3, where the table's
+    unsigned pixel = 0, qidx = 0;    // the lane's task: its pixel and its chunk-partial index (decode_task e[1], e[0])
+    bool owns = false;               // the lane's LDS sums belong to that task
+    // every instantiation but the deep-tree ones (QB 3 and 5, where the table's
     // registers cost spills): each wave decodes its batches of tasks into LDS
     constexpr bool TTAB = !DEEP;
     __shared__ uint32_t ttab_lds[TTAB ? 4 * kTaskWords * 64 : 1];
-    unsigned qidx = 0;               // (TTAB) partial index of the lane's task
     Stream st;                       // draw stream of the sample in flight (next31 for refraction / AO)
     st.start(0u, 0u, kp.key0, kp.key1, rng);
     // shallow trees (QB 4: depth4 <= 4, e.g. the 50-node sweep tree) keep
@@ -533,26 +528,28 @@ void render_kernel_q(const KParams kp)
             // launch constants re-read here (SMEM) instead of living in SGPRs
             // spilled to VGPR lanes across the whole round
             const KParamsK K = kp_here();
-            unsigned t = 0;
             const unsigned nn = (unsigned)__popcll(nm), avail = qe - qb;
             const unsigned rank = (unsigned)__popcll(nm & ((1ull << lane) - 1ull));
-            if constexpr (TTAB) {
-                // a batch's 64 tasks are decoded once, by the whole wave, into the
-                // wave's LDS table when the batch is grabbed; a lane taking a task
-                // reads its entry: lanes taking the rest of the current batch
-                // before the new batch overwrites the table, the others after
-                uint32_t* tw = ttab_lds + (threadIdx.x >> 6) * (kTaskWords * 64);
-                const bool old = rank < avail;
-                uint32_t e[kTaskWords];
-                if (need && old) {
-                    const unsigned slot = (qb - (qe - kQueueBatch)) + rank;
+            // lanes take the rest of the current batch first (old), the others the
+            // new batch's first tasks.  TTAB: a batch's 64 tasks are decoded once,
+            // by the whole wave, into the wave's LDS table when the batch is
+            // grabbed; a lane taking a task reads its entry, old lanes before the
+            // new batch overwrites the table.  Otherwise a lane decodes its own
+            // task t in registers.
+            const bool old = rank < avail;
+            uint32_t* tw = ttab_lds + (threadIdx.x >> 6) * (kTaskWords * 64);
+            unsigned t = qb + rank;
+            uint32_t e[kTaskWords];
+            if (TTAB && need && old) {
+                const unsigned slot = (qb - (qe - kQueueBatch)) + rank;
 #pragma unroll
-                    for (int j = 0; j < kTaskWords; ++j) e[j] = tw[j * 64 + slot];
-                }
-                if (avail < nn) {
-                    unsigned nb = 0;
-                    if (lane == __ffsll((long long)nm) - 1) nb = atomicAdd(K->task_ctr, (unsigned)kQueueBatch);
-                    nb = __shfl(nb, __ffsll((long long)nm) - 1, 64);
+                for (int j = 0; j < kTaskWords; ++j) e[j] = tw[j * 64 + slot];
+            }
+            if (avail < nn) {            // a new batch (nn <= 64)
+                unsigned nb = 0;
+                if (lane == __ffsll((long long)nm) - 1) nb = atomicAdd(K->task_ctr, (unsigned)kQueueBatch);
+                nb = __shfl(nb, __ffsll((long long)nm) - 1, 64);
+                if constexpr (TTAB) {
                     uint32_t d[kTaskWords];
                     decode_task(K, nb + (unsigned)lane, d);
 #pragma unroll
@@ -561,79 +558,36 @@ void render_kernel_q(const KParams kp)
 #pragma unroll
                         for (int j = 0; j < kTaskWords; ++j) e[j] = tw[j * 64 + (rank - avail)];
                     }
-                    qb = nb + (nn - avail);
-                    qe = nb + kQueueBatch;
-                } else {
-                    qb += nn;
+                } else if (!old) {
+                    t = nb + (rank - avail);
                 }
-                if (need) {
-                    ++ntasks;
-                    if (owns) {      // task done: its sums to the chunk partials
-                        double* q = K->partial + (size_t)qidx * 9;
-#pragma unroll
-                        for (int j = 0; j < 9; ++j) q[j] = acc[j * 256];
-                        owns = false;
-                    }
-                    if (e[0] == 0xffffffffu) {
-                        L.state = SM_DONE;
-                    } else if (e[1] != 0xffffffffu) {  // otherwise the lane takes its next task next round
-                        qidx = e[0];
-                        pixel = e[1];
-                        g = (int)e[2];
-                        x = (int)(pixel - e[2] * (unsigned)K->W);
-                        L.s = (int)e[3];
-                        s1 = (int)e[4];
-#pragma unroll
-                        for (int j = 0; j < 9; ++j) acc[j * 256] = 0.0;
-                        owns = true;
-                    }
-                }
-            } else {
-            if (avail < nn) {        // a new batch (nn <= 64): old tasks first
-                unsigned nb = 0;
-                if (lane == __ffsll((long long)nm) - 1) nb = atomicAdd(K->task_ctr, (unsigned)kQueueBatch);
-                nb = __shfl(nb, __ffsll((long long)nm) - 1, 64);
-                t = rank < avail ? qb + rank : nb + (rank - avail);
                 qb = nb + (nn - avail);
                 qe = nb + kQueueBatch;
             } else {
-                t = qb + rank;
                 qb += nn;
             }
             if (need) {
+                if constexpr (!TTAB) decode_task(K, t, e);
                 ++ntasks;
-                if (owns) {          // task done: its sums to the chunk partials
-                    double* q = K->partial + ((size_t)chunk * ((unsigned)K->band_rows * (unsigned)K->W) + p) * 9;
+                if (owns) {              // task done: its sums to the chunk partials
+                    double* q = K->partial + (size_t)qidx * 9;
 #pragma unroll
                     for (int j = 0; j < 9; ++j) q[j] = acc[j * 256];
                     owns = false;
                 }
-                if (t >= K->npx_here * (unsigned)K->chunks) {
+                if (e[0] == 0xffffffffu) {
                     L.state = SM_DONE;
-                } else {
-                    // task t = (chunk, pixel p of the band): launch-constant divisors
-                    chunk = udiv_q(t, K->npx_here, K->qm_npx, p);
-                    unsigned xr;
-                    const unsigned row = udiv_q(p, (unsigned)K->W, K->qm_w, xr);
-                    const int ly = K->band_y0 + (int)row;
-                    x = (int)xr;
-                    bool valid = ly < K->local_rows;
-                    if (valid) {
-                        unsigned yy;
-                        const int lt = (int)udiv_q((unsigned)ly, (unsigned)K->tile_rows, K->qm_tile, yy);
-                        g = K->row_base + (K->tile_first + lt * K->tile_step) * K->tile_rows + (int)yy;
-                        valid = g < K->row_end;
-                    }
-                    if (valid) {     // otherwise the lane takes its next task next round
-                        pixel = (uint32_t)g * (uint32_t)K->W + (uint32_t)x;
-                        L.s = chunk_start(K->S, K->chunks, K->chunk_taper, K->chunk_den, K->qm_chunks, chunk);
-                        s1 = chunk_start(K->S, K->chunks, K->chunk_taper, K->chunk_den, K->qm_chunks, chunk + 1u);
+                } else if (e[1] != 0xffffffffu) {  // else a padding row: the lane takes its next task next round
+                    qidx = e[0];
+                    pixel = e[1];
+                    g = (int)e[2];
+                    x = (int)(pixel - e[2] * (unsigned)K->W);
+                    L.s = (int)e[3];
+                    s1 = (int)e[4];
 #pragma unroll
-                        for (int j = 0; j < 9; ++j) acc[j * 256] = 0.0;
-                        owns = true;
-                    }
+                    for (int j = 0; j < 9; ++j) acc[j * 256] = 0.0;
+                    owns = true;
                 }
-            }
             }
         }
         if (__ballot(L.state != SM_DONE) == 0ull) break;     // every lane of the wave is done
@@ -696,29 +650,7 @@ void render_kernel_q(const KParams kp)
             V3 no = v3(0, 0, 0);
             if (cam) {
                 CamDraws w{blk, 0};
-                const double ju = rand_m05(w.next31());     // randomDouble(-0.5, 0.5)
-                const double jv = rand_m05(w.next31());
-                const int b = opq0();
-                const cdptr U = (cdptr)kp.uni;
-                const double nu = (double)x + ju, nv = (double)g + jv;
-                const double rcw = U[b + U_RC_WM1], rch = U[b + U_RC_HM1];
-                const double u = rcw != 0.0 ? div_core(nu, U[b + U_WM1], rcw) : nu / U[b + U_WM1];
-                const double v = rch != 0.0 ? div_core(nv, U[b + U_HM1], rch) : nv / U[b + U_HM1];
-                const V3 co = v3(U[b + U_CAM_O], U[b + U_CAM_O + 1], U[b + U_CAM_O + 2]);
-                const V3 ch = v3(U[b + U_CAM_H], U[b + U_CAM_H + 1], U[b + U_CAM_H + 2]);
-                const V3 cv = v3(U[b + U_CAM_V], U[b + U_CAM_V + 1], U[b + U_CAM_V + 2]);
-                const V3 cc = v3(U[b + U_CAM_C], U[b + U_CAM_C + 1], U[b + U_CAM_C + 2]);
-                const V3 dir = cc + (muls(ch, u) + (muls(cv, v) - co));     // get_ray, camera.h:42-55
-                const V3 dest = co + muls(dir, U[b + U_FOCUS]);
-                if (kp.cam_pin) {                              // zero aperture: the origin itself (host-checked)
-                    no = co;
-                } else {
-                    const double jx = rand_m05(w.next31());
-                    const double jy = rand_m05(w.next31());
-                    const double dx = jx * U[b + U_OX], dy = jy * U[b + U_OY];
-                    no = co + v3(dx, dy, 0);
-                }
-                X = dest - no;
+                X = camera_ray_raw<false>(kp, x, g, w, kp.cam_pin != 0, no);
             } else {
                 // random_dir_no_norm (rtutility.h:189-203), then n + dir (main.c:163)
                 X = H.hn + normalize_unit(sampler_vec(wa >> 1, wb >> 1));

@@ -309,6 +309,7 @@ __device__ __forceinline__ void box4(const KParams& kp, const BvhNode4* nd, cons
     Cn[0] = cnt4.x; Cn[1] = cnt4.y; Cn[2] = cnt4.z; Cn[3] = cnt4.w;
     const float Px[4] = {px.x, px.y, px.z, px.w}, Py[4] = {py.x, py.y, py.z, py.w}, Pz[4] = {pz.x, pz.y, pz.z, pz.w};
     const float Qx[4] = {qx.x, qx.y, qx.z, qx.w}, Qy[4] = {qy.x, qy.y, qy.z, qy.w}, Qz[4] = {qz.x, qz.y, qz.z, qz.w};
+    // box4h's slab loop, with the ray's own offsets
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const float tmin = fmaxf(fmaxf(fmaf(Px[c], r.ix, r.ax), fmaf(Py[c], r.iy, r.ay)), fmaf(Pz[c], r.iz, r.az));
@@ -372,6 +373,7 @@ __device__ __forceinline__ void box4h(const KParams& kp, const BvhNodeH* nd, uin
     const float Qx[4] = {h16lo(qx.x), h16hi(qx.x), h16lo(qx.y), h16hi(qx.y)};
     const float Qy[4] = {h16lo(qy.x), h16hi(qy.x), h16lo(qy.y), h16hi(qy.y)};
     const float Qz[4] = {h16lo(qz.x), h16hi(qz.x), h16lo(qz.y), h16hi(qz.y)};
+    // box4's slab loop, with the node origin folded into the offsets
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const int nib = (int)((cn >> (4 * c)) & 15u);
@@ -385,10 +387,14 @@ __device__ __forceinline__ void box4h(const KParams& kp, const BvhNodeH* nd, uin
     }
 }
 
-// One node visit: the four child boxes, the triangles of the hit leaves, then
-// the next node (nearest hit internal child, else the stack top).  Returns
-// false when the traversal is over.  tris_bvh loops it to the end; the
-// resumable trace (render_sm) runs a bounded number of visits per round.
+// One node visit (bvh_visit): the four child boxes, the triangles of the hit
+// leaves, then the next node (nearest hit internal child, else the stack top).
+// Returns false when the traversal is over.  Every other hit internal child goes
+// to the caller's sink other(node, its entry distance): bvh_step pushes it on
+// the lane's stack (bvh_push); the fixed grid's cooperative walk (samples_coop,
+// rt_fixed_grid.h) hands it to the wave's LIFO while that has room.  tris_bvh
+// loops bvh_step to the end; the queue kernel (render_kernel_q) and samples_coop
+// run a bounded number of visits per round.
 __device__ __forceinline__ float* diag_lds()
 {
     __shared__ float dg_lds[RT_DIAG_STALE ? 17 * 256 : 1];
@@ -400,13 +406,15 @@ __device__ __forceinline__ unsigned* diag_cnt()
     return dc_lds + threadIdx.x;
 }
 // H: 0 the 128-byte nodes, 1 BvhNodeH, 2 BvhNodeW; STK: the lane's stack (a
-// uint16 or uint32 column, or the QB 5 kernel's Stack24; stk_put / stk_get)
-template <bool COUNT, bool CU, int NTOP = 0, int H = 0, class STK>
-__device__ __forceinline__ bool bvh_step(const KParams& kp, const V3 o, const V3 d, const Ray32& r32,
-                                         STK stk, int& node, int& sp, double& best, int& kind,
-                                         int& win, int& win_orig, Cnt& cnt, const void* top = nullptr)
+// uint16 or uint32 column, or the QB 5 kernel's Stack24; stk_put / stk_get);
+// DG: the RT_DIAG_STALE bookkeeping of a lane's own walk (entry distances of the
+// node in hand, slot 16, and of the stack entries below depth 16)
+template <bool COUNT, bool CU, int NTOP, int H, bool DG, class STK, class SINK>
+__device__ __forceinline__ bool bvh_visit(const KParams& kp, const V3 o, const V3 d, const Ray32& r32,
+                                          STK stk, int& node, int& sp, double& best, int& kind,
+                                          int& win, int& win_orig, Cnt& cnt, const void* top, SINK other)
 {
-    if constexpr (RT_DIAG_STALE && (COUNT || RT_DIAG_STALE == 2)) {
+    if constexpr (DG) {
         float* dg = diag_lds();
         if (node == 0) dg[16 * 256] = -__builtin_huge_valf();          // the root: a new walk
         const bool stale = dg[16 * 256] > cull32(kp, best);
@@ -456,13 +464,7 @@ __device__ __forceinline__ bool bvh_step(const KParams& kp, const V3 o, const V3
                 next = ch;
                 tnext = tn[c];
             }
-            if (!RT_DIAG_STALE && COUNT && sp >= kp.stack_cap) cnt.c[RT_CNT_BVH_STACK_OVER] += 1;
-            if (!COUNT || sp < kStack4) {    // COUNT walks use the fixed grid's stack
-                if (RT_DIAG_STALE && (COUNT || RT_DIAG_STALE == 2) && sp < 16) diag_lds()[sp * 256] = tpush;
-                stk_put(stk, sp, push);
-                ++sp;
-            }
-            (void)tpush;
+            other(push, tpush);
         }
     }
     // The triangles of every hit leaf in one loop, one triangle per lane and
@@ -483,15 +485,41 @@ __device__ __forceinline__ bool bvh_step(const KParams& kp, const V3 o, const V3
     }
     if (next >= 0) {
         node = next;
-        if (RT_DIAG_STALE && (COUNT || RT_DIAG_STALE == 2)) diag_lds()[16 * 256] = tnext;
+        if (DG) diag_lds()[16 * 256] = tnext;
         return true;
     }
     if (sp == 0) return false;
     --sp;
     node = stk_get(stk, sp);
-    if (RT_DIAG_STALE && (COUNT || RT_DIAG_STALE == 2))
-        diag_lds()[16 * 256] = sp < 16 ? diag_lds()[sp * 256] : -__builtin_huge_valf();
+    if (DG) diag_lds()[16 * 256] = sp < 16 ? diag_lds()[sp * 256] : -__builtin_huge_valf();
     return true;
+}
+
+// A hit internal child that is not entered next, onto the lane's stack (tpush:
+// its entry distance).  COUNT walks use the fixed grid's stack and check every
+// push against the stack of the kernel the launch would take (kp.stack_cap).
+template <bool COUNT, bool DG, class STK>
+__device__ __forceinline__ void bvh_push(const KParams& kp, STK stk, int& sp, int push, float tpush, Cnt& cnt)
+{
+    if (!RT_DIAG_STALE && COUNT && sp >= kp.stack_cap) cnt.c[RT_CNT_BVH_STACK_OVER] += 1;
+    if (!COUNT || sp < kStack4) {
+        if (DG && sp < 16) diag_lds()[sp * 256] = tpush;
+        stk_put(stk, sp, push);
+        ++sp;
+    }
+}
+
+// A node visit of a lane's own walk: the other children go on its stack.
+template <bool COUNT, bool CU, int NTOP = 0, int H = 0, class STK>
+__device__ __forceinline__ bool bvh_step(const KParams& kp, const V3 o, const V3 d, const Ray32& r32,
+                                         STK stk, int& node, int& sp, double& best, int& kind,
+                                         int& win, int& win_orig, Cnt& cnt, const void* top = nullptr)
+{
+    constexpr bool DG = RT_DIAG_STALE && (COUNT || RT_DIAG_STALE == 2);
+    return bvh_visit<COUNT, CU, NTOP, H, DG>(kp, o, d, r32, stk, node, sp, best, kind, win, win_orig, cnt, top,
+                                            [&](int push, float tpush) __attribute__((always_inline)) {
+                                                bvh_push<COUNT, DG>(kp, stk, sp, push, tpush, cnt);
+                                            });
 }
 
 template <bool COUNT, bool CU, class SE = unsigned short>
