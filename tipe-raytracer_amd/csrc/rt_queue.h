@@ -74,8 +74,13 @@ struct QHit {
 // resolve_hit to finish_bounce instead of redoing the barycentrics (the
 // brute-force kernel, QB 0: C3 +7.0 %, C5 +6.7 %; the BVH kernels recompute,
 // their registers are tighter: sweep -1.9 % with KT)
-template <bool SKY, int AOM, bool NT = false, bool OP = false, int IR = 0, bool KT = false>   // IR 1: incomingLight only
+// PD: paired draws (render_kernel_q's step 4): OP without AO; then resolve_hit
+// moves o to the hit point of every hit (a lit lane's path is over, its o is
+// dead) and skips the miss's identity adds
+template <bool SKY, int AOM, bool NT = false, bool OP = false, int IR = 0, bool KT = false,   // IR 1: incomingLight only
+          bool PD = false>
 struct QPath {
+    static_assert(!PD || (OP && AOM != AO_ON), "paired draws: two draws per bounce, none else");
     V3 o, d, cd, inc, rc;            // cd: the cast's direction (AO casts; else d)
     double* accp;                    // (IR) the lane's LDS column
     double top_n2, best;
@@ -258,7 +263,11 @@ struct QPath {
             }
             pend = false;
         } else if (kind == HIT_NONE) {                   // miss: the path ends, main.c:236-238
-            if (chain) {
+            // PD: tracer's two adds of (0, 0, 0) are identities and are not made.
+            // A task's sums start at +0.0 and x + y (round to nearest) is -0
+            // only when x and y both are, so by induction no sum is ever -0;
+            // s + (+0) is s bit for bit for every other s (NaN, infinity too).
+            if (!PD && chain) {
                 acc_add(acc, ACC_ALB, v3(0, 0, 0));
                 acc_add(acc, ACC_NRM, v3(0, 0, 0));
             }
@@ -270,6 +279,10 @@ struct QPath {
                 nw = win;
                 nk = kind;
                 nrm = true;
+            } else if (PD) {                             // the hit point straight into o (hit_rest's
+                o = o + muls(d, best);                   // o = hp for the lanes that go on): no copy
+                H.hn = hit_normal(kp, o, kind, win);     // of o at the merge with the missing lanes
+                hit_rest(o);
             } else {
                 const V3 hp = o + muls(d, best);         // ray_at
                 H.hn = hit_normal(kp, hp, kind, win);
@@ -406,8 +419,17 @@ void render_kernel_q(const KParams kp)
     uint32_t* rng = rng_lds + threadIdx.x;
     const int lane = threadIdx.x & 63;
     unsigned qb = 0, qe = 0;         // the wave's batch of tasks [qb, qe) (wave-uniform)
-    QPath<SKY, AOM, QB < 0, QB == -2 || OPQ, QIR, QB == 0> L;
+    // Paired draws: every material opaque and no AO, so a sample's draws are
+    // fixed -- the camera takes draws 0-3 (Philox block 0) and bounce i draws
+    // 4 + 2i and 5 + 2i: a bounce with even i opens block 1 + i/2, uses its
+    // words 0, 1 and keeps words 2, 3 (kw2, kw3) for bounce i + 1.  Step 4 then
+    // needs neither the draw count st.n nor the block cache in LDS.  The
+    // sphere-only kernels take this form; the opaque deep-tree kernel (QB 3,
+    // OPQ) has no registers to spare and keeps the general one.
+    constexpr bool PD = QB == -2 && AOM != AO_ON;
+    QPath<SKY, AOM, QB < 0, QB == -2 || OPQ, QIR, QB == 0, PD> L;
     L.init(acc);
+    uint32_t kw2 = 0, kw3 = 0;       // (PD) the kept words of the sample's current block
 #if RT_DIAG_STALE == 2
     diag_cnt()[0] = 0u;
     diag_cnt()[256] = 0u;
@@ -613,7 +635,23 @@ void render_kernel_q(const KParams kp)
             const uint32_t sa = nd & 3u, sb = (nd + 1u) & 3u;
             uint32_t wa = 0, wb = 0;
             Philox blk{0, 0, 0, 0};
-            if (pbr) {
+            Philox pblk;                 // (PD) its block: read by camera lanes alone, which make it
+            if constexpr (PD) {
+                // the same words of the same blocks as below, from L.i instead of
+                // st.n (n = 4 + 2i).  A camera lane's block leaves kw2, kw3 what its
+                // sample never reads: bounce 0 opens block 1.
+                if (cam || (L.i & 1) == 0) {
+                    const uint32_t bi = cam ? 0u : 1u + ((uint32_t)L.i >> 1);
+                    pblk = philox4x32_10(bi, 0u, pixel, (uint32_t)(kp.s_base + L.s), kp.key0, kp.key1);
+                    wa = pblk.w0;
+                    wb = pblk.w1;
+                    kw2 = pblk.w2;
+                    kw3 = pblk.w3;
+                } else {
+                    wa = kw2;
+                    wb = kw3;
+                }
+            } else if (pbr) {
                 wa = rng[0];
                 wb = rng[256];
             } else {
@@ -649,16 +687,17 @@ void render_kernel_q(const KParams kp)
             V3 X;
             V3 no = v3(0, 0, 0);
             if (cam) {
-                CamDraws w{blk, 0};
-                X = camera_ray_raw<false>(kp, x, g, w, kp.cam_pin != 0, no);
+                CamDraws w{PD ? pblk : blk, 0};
+                // (PD) the origin straight into L.o: only camera lanes are here
+                X = camera_ray_raw<false>(kp, x, g, w, kp.cam_pin != 0, PD ? L.o : no);
             } else {
                 // random_dir_no_norm (rtutility.h:189-203), then n + dir (main.c:163)
                 X = H.hn + normalize_unit(sampler_vec(wa >> 1, wb >> 1));
-                st.n += aor ? 0u : pbr ? 4u : 2u;
+                if (!PD) st.n += aor ? 0u : pbr ? 4u : 2u;
             }
             const V3 dn = normalize(X);
             if (cam) {                                         // the new sample's primary ray
-                L.o = no;
+                if (!PD) L.o = no;
                 L.d = dn;
                 if (AOM == AO_ON) L.cd = dn;
                 L.inc_set(v3(0, 0, 0));
@@ -668,8 +707,10 @@ void render_kernel_q(const KParams kp)
                 L.chain = true;
                 L.ao_cast = false;
                 L.state = SM_CAST;
-                st.start(pixel, (uint32_t)(kp.s_base + L.s), kp.key0, kp.key1, rng);
-                st.n = 4;                                      // draws 0-3 were the camera's
+                if (!PD) {
+                    st.start(pixel, (uint32_t)(kp.s_base + L.s), kp.key0, kp.key1, rng);
+                    st.n = 4;                                  // draws 0-3 were the camera's
+                }
             } else if (aor) {                                  // ambient_occlusion's cast (main.c:96-103)
                 L.cd = dn;
                 L.ao_cast = true;
