@@ -112,6 +112,23 @@ int first_device(int& dev)
     return rc;
 }
 
+int validate_denoise(int W, int H, const rt_denoise_params* p)
+{
+    if (W < 1 || H < 1) return fail(RT_EINVAL, "denoise: frame %dx%d", W, H);
+    if ((long long)W * H > (1ll << 30)) return fail(RT_EINVAL, "denoise: frame %dx%d above 2^30 pixels", W, H);
+    if (!p) return fail(RT_EINVAL, "denoise: params is NULL");
+    if (p->iterations < 1 || p->iterations > 8)
+        return fail(RT_EINVAL, "denoise: iterations %d outside 1..8", p->iterations);
+    const float sig[3] = {p->sigma_color, p->sigma_normal, p->sigma_albedo};
+    const char* const name[3] = {"sigma_color", "sigma_normal", "sigma_albedo"};
+    for (int i = 0; i < 3; ++i) {
+        if (!std::isfinite(sig[i])) return fail(RT_EINVAL, "denoise: %s is not finite", name[i]);
+        if (sig[i] < 0x1p-8f || sig[i] > 0x1p8f)
+            return fail(RT_EINVAL, "denoise: %s %g outside [2^-8, 2^8]", name[i], (double)sig[i]);
+    }
+    return RT_OK;
+}
+
 int validate_scene(const rt_scene* sc)
 {
     if (!sc) return fail(RT_EINVAL, "scene is NULL");
@@ -559,6 +576,39 @@ int rt_denoise_pack_async(int W, int H, const rt_frame* frame, float* color3, fl
                                       normal3 ? (const double*)frame->normal : nullptr, color3, albedo3, normal3,
                                       hip_stream);
     if (e) return fail(RT_EDEVICE, "denoise pack launch: %s", hipGetErrorString((hipError_t)e));
+    return RT_OK;
+}
+
+void rt_denoise_params_init(rt_denoise_params* p)
+{
+    if (!p) return;
+    p->iterations = 4;
+    p->sigma_color = 1.0f;
+    p->sigma_normal = 0.5f;
+    p->sigma_albedo = 0.25f;
+}
+
+size_t rt_denoise_workspace_bytes(int W, int H)
+{
+    if (W < 1 || H < 1 || (long long)W * H > (1ll << 30)) return 0;
+    return 4 * denoise_plane_floats((long long)W * H) * sizeof(float);
+}
+
+int rt_denoise_async(int W, int H, const rt_frame* frame, const rt_denoise_params* params, void* workspace,
+                     size_t workspace_bytes, float* color3_out, void* hip_stream)
+{
+    const int rc = validate_denoise(W, H, params);
+    if (rc) return rc;
+    if (!frame || !frame->canva) return fail(RT_EINVAL, "denoise: canva is NULL");
+    if (!workspace) return fail(RT_EINVAL, "denoise: workspace is NULL");
+    if ((uintptr_t)workspace % 16) return fail(RT_EINVAL, "denoise: workspace is not 16-byte aligned");
+    if (workspace_bytes < rt_denoise_workspace_bytes(W, H))
+        return fail(RT_EINVAL, "denoise: workspace of %zu bytes, %dx%d needs %zu", workspace_bytes, W, H,
+                    rt_denoise_workspace_bytes(W, H));
+    const int e = launch_denoise(W, H, (double*)frame->canva, (const double*)frame->albedo,
+                                 (const double*)frame->normal, params->iterations, params->sigma_color,
+                                 params->sigma_normal, params->sigma_albedo, (float*)workspace, color3_out, hip_stream);
+    if (e) return fail(RT_EDEVICE, "denoise launch: %s", hipGetErrorString((hipError_t)e));
     return RT_OK;
 }
 

@@ -64,6 +64,7 @@ int first_device(int& dev);
 
 int validate_scene(const rt_scene* sc);
 int validate_params(const rt_params* p);
+int validate_denoise(int W, int H, const rt_denoise_params* p);   // frame size and parameters of the built-in denoiser
 
 void make_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling* t, KParams& kp, double* uni);
 int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count);

@@ -21,6 +21,8 @@ using namespace rt;
 namespace {
 
 std::atomic<rt_denoise_fn> g_denoise{nullptr};
+std::mutex g_denoise_mu;
+rt_denoise_params g_denoise_params = {4, 1.0f, 0.5f, 0.25f};   // rt_denoise_atrous's; rt_denoise_params_init's defaults
 
 // ---- host-buffer drop-in plumbing (rt_render_rows / rt_fill_canva) --------
 // main.c runs fill_canva on NUM_THREADS pthreads (main.c:404-453); each of
@@ -622,6 +624,72 @@ int rt_denoise_unpack(int W, int H, const float* color3, rt_color* canva)
     for (size_t i = 0; i < n; ++i)
         for (int c = 0; c < 3; ++c) canva[i].e[c] = (int)(color3[3 * i + c] * 255.0f);   // denoiser.h:80-84
     return RT_OK;
+}
+
+int rt_denoise_host(int W, int H, rt_color* canva, const rt_color* albedo, const rt_color* normal,
+                    const rt_denoise_params* params)
+{
+    int rc, dev;
+    if ((rc = validate_denoise(W, H, params))) return rc;
+    if (!canva) return fail(RT_EINVAL, "denoise: canva is NULL");
+    if ((rc = first_device(dev))) return rc;
+    PooledStream* ps = nullptr;
+    if ((rc = stream_pool_get(dev, &ps))) return rc;
+    DeviceGuard g(dev);
+    const size_t plane = (size_t)W * H * sizeof(rt_color), ws_bytes = rt_denoise_workspace_bytes(W, H);
+    const rt_color* src[3] = {canva, albedo, normal};
+    char* buf = nullptr;             // device: the workspace, then the given planes
+    auto done = [&](int code) {
+        if (buf) (void)hipFreeAsync(buf, ps->st);
+        (void)hipStreamSynchronize(ps->st);
+        stream_pool_put(ps);
+        return code;
+    };
+    hipError_t e = ps->reserve_host(3 * plane);
+    if (e == hipSuccess) e = hipMallocAsync((void**)&buf, ws_bytes + 3 * plane, ps->st);
+    if (e != hipSuccess) return done(fail(RT_ENOMEM, "denoise buffers: %s", hipGetErrorString(e)));
+    rt_frame fr = {nullptr, nullptr, nullptr, nullptr};
+    rt_color** dst[3] = {&fr.canva, &fr.albedo, &fr.normal};
+    for (int pl = 0; pl < 3 && e == hipSuccess; ++pl) {
+        if (!src[pl]) continue;
+        char* host = (char*)ps->host + pl * plane;
+        std::memcpy(host, src[pl], plane);
+        *dst[pl] = (rt_color*)(buf + ws_bytes + pl * plane);
+        e = hipMemcpyAsync(*dst[pl], host, plane, hipMemcpyHostToDevice, ps->st);
+    }
+    if (e != hipSuccess) return done(fail(RT_EDEVICE, "denoise upload: %s", hipGetErrorString(e)));
+    if ((rc = rt_denoise_async(W, H, &fr, params, buf, ws_bytes, nullptr, ps->st))) return done(rc);
+    e = hipMemcpyAsync(ps->host, fr.canva, plane, hipMemcpyDeviceToHost, ps->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(ps->st);
+    if (e != hipSuccess) return done(fail(RT_EDEVICE, "denoise: %s", hipGetErrorString(e)));
+    std::memcpy(canva, ps->host, plane);
+    return done(RT_OK);
+}
+
+int rt_set_denoise_params(const rt_denoise_params* params)
+{
+    rt_denoise_params p;
+    rt_denoise_params_init(&p);
+    if (params) {
+        const int rc = validate_denoise(1, 1, params);
+        if (rc) return rc;
+        p = *params;
+    }
+    std::lock_guard<std::mutex> lk(g_denoise_mu);
+    g_denoise_params = p;
+    return RT_OK;
+}
+
+void rt_denoise_atrous(int largeur_image, int hauteur_image, rt_color* canva, rt_camera cam, rt_color* albedo,
+                       rt_color* normal)
+{
+    (void)cam;
+    rt_denoise_params p;
+    {
+        std::lock_guard<std::mutex> lk(g_denoise_mu);
+        p = g_denoise_params;
+    }
+    (void)rt_denoise_host(largeur_image, hauteur_image, canva, albedo, normal, &p);
 }
 
 void* rt_fill_canva(void* arg)

@@ -203,5 +203,11 @@ int launch_verify_texel(const KParams& kp, const double* d_pts, const int* d_tri
 int launch_resolve(const KParams& kp, void* stream);
 int launch_denoise_pack(long long npx, const double* canva, const double* albedo, const double* normal,
                         float* color3, float* albedo3, float* normal3, void* stream);
+// launchers (rt_denoise.hip): the built-in a-trous denoiser (rt.h "built-in denoiser") on a device frame.
+// The workspace holds four planes of denoise_plane_floats(W*H) floats; albedo / normal may be null.
+size_t denoise_plane_floats(long long npx);
+int launch_denoise(int W, int H, double* canva, const double* albedo, const double* normal, int iterations,
+                   float sigma_color, float sigma_normal, float sigma_albedo, float* workspace, float* color3_out,
+                   void* stream);
 
 }  // namespace rt

@@ -6,6 +6,11 @@
  *
  *   rt_demo [-w W] [-s spp] [-b nbRebondMax] [-ao AO_intensity] [-o out.ppm]
  *           [-obj file.obj -mtl file.mtl [-move x y z]] [-devices N]
+ *           [-denoise [iterations]]
+ *
+ * -denoise installs the library's built-in a-trous filter (rt_denoise_atrous;
+ * not OIDN, and biased: meant for low-spp frames) as the denoiser hook before
+ * the render, with `iterations` passes (default 4; more for larger frames).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -20,7 +25,9 @@
 
 int main(int argc, char** argv)
 {
-    int W = 400, spp = 100, bounces = 5, ndev = 1, useAO = 0;
+    int W = 400, spp = 100, bounces = 5, ndev = 1, useAO = 0, denoise = 0;
+    rt_denoise_params dn;
+    rt_denoise_params_init(&dn);
     double AO = 2.5, mx = 0, my = 0, mz = 0;
     const char *out = "render.ppm", *obj = NULL, *mtl = NULL;
     for (int i = 1; i < argc; i++) {
@@ -32,13 +39,17 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-obj") && i + 1 < argc) obj = argv[++i];
         else if (!strcmp(argv[i], "-mtl") && i + 1 < argc) mtl = argv[++i];
         else if (!strcmp(argv[i], "-devices") && i + 1 < argc) ndev = atoi(argv[++i]);
-        else if (!strcmp(argv[i], "-move") && i + 3 < argc) {
+        else if (!strcmp(argv[i], "-denoise")) {
+            denoise = 1;
+            if (i + 1 < argc && argv[i + 1][0] != '-') dn.iterations = atoi(argv[++i]);
+        } else if (!strcmp(argv[i], "-move") && i + 3 < argc) {
             mx = atof(argv[++i]);
             my = atof(argv[++i]);
             mz = atof(argv[++i]);
         } else {
             fprintf(stderr, "usage: %s [-w W] [-s spp] [-b bounces] [-ao I] [-o out.ppm] "
-                            "[-obj f.obj -mtl f.mtl [-move x y z]] [-devices N]\n", argv[0]);
+                            "[-obj f.obj -mtl f.mtl [-move x y z]] [-devices N] [-denoise [iterations]]\n",
+                    argv[0]);
             return 2;
         }
     }
@@ -97,6 +108,10 @@ int main(int argc, char** argv)
         int devs[64];
         for (int i = 0; i < ndev && i < 64; i++) devs[i] = i;
         if (rt_init(ndev, devs)) { fprintf(stderr, "rt_init: %s\n", rt_last_error()); return 1; }
+    }
+    if (denoise) {      /* main.c:455 with useDenoiser: the built-in filter instead of OIDN */
+        if (rt_set_denoise_params(&dn)) { fprintf(stderr, "-denoise: %s\n", rt_last_error()); return 1; }
+        rt_set_denoise_hook(rt_denoise_atrous);
     }
     size_t n = (size_t)W * H;
     rt_color* canva = (rt_color*)calloc(n, sizeof(rt_color));

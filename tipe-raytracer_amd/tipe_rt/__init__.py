@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from .types import (Vec3, Ray, Material, Sphere, UV, Triangle, Camera, ThreadData, Scene,  # noqa: F401
-                    Params, Tiling, Frame, RT_OK, RT_EINVAL, RT_EDEVICE, RT_ENOMEM, RT_EUNSUPPORTED,
+                    Params, Tiling, Frame, DenoiseParams, RT_OK, RT_EINVAL, RT_EDEVICE, RT_ENOMEM, RT_EUNSUPPORTED,
                     RT_RNG_PHILOX, RT_RNG_GLIBC, RT_NCOUNTERS, COUNTER_NAMES, RT_SPP_CHUNKS_AUTO,
                     RT_SPP_CHUNKS_DEFAULT)
 
@@ -86,6 +86,16 @@ def lib():
         L.rt_denoise_pack.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6
         L.rt_denoise_unpack.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.rt_denoise_pack_async.argtypes = [C.c_int, C.c_int, P(Frame)] + [C.c_void_p] * 4
+        L.rt_denoise_params_init.argtypes = [P(DenoiseParams)]
+        L.rt_denoise_params_init.restype = None
+        L.rt_denoise_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        L.rt_denoise_workspace_bytes.restype = C.c_size_t
+        L.rt_denoise_async.argtypes = [C.c_int, C.c_int, P(Frame), P(DenoiseParams), C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.c_void_p]
+        L.rt_denoise_host.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, P(DenoiseParams)]
+        L.rt_denoise_atrous.argtypes = [C.c_int, C.c_int, C.c_void_p, Camera, C.c_void_p, C.c_void_p]
+        L.rt_denoise_atrous.restype = None
+        L.rt_set_denoise_params.argtypes = [P(DenoiseParams)]
         _lib = L
     return _lib
 
@@ -97,7 +107,8 @@ EXPORTED_SYMBOLS = ["rt_params_init", "rt_init", "rt_shutdown", "rt_last_error",
                     "rt_denoise_unpack", "rt_denoise_pack_async", "rt_verify_sampler_phi",
                     "rt_verify_sphere_pass", "rt_verify_normalize", "rt_verify_texel_map", "rt_set_zero_throughput_exit", "rt_set_fill_spp_chunks", "rt_set_fill_precision",
                     "rt_scene_cache_clear", "rt_gather_async", "rt_render_gather_async", "rt_peer_access",
-                    "rt_last_render_kernel"]
+                    "rt_last_render_kernel", "rt_denoise_params_init", "rt_denoise_workspace_bytes",
+                    "rt_denoise_async", "rt_denoise_host", "rt_denoise_atrous", "rt_set_denoise_params"]
 
 # rt_denoise_fn (rt.h): denoiser()'s signature, denoiser.h:31
 DENOISE_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p, Camera, C.c_void_p, C.c_void_p)
@@ -150,6 +161,46 @@ def denoise_unpack(color3):
     c = np.ascontiguousarray(color3, dtype=np.float32)
     check(lib().rt_denoise_unpack(W, H, c.ctypes.data, out.ctypes.data))
     return out
+
+
+def denoise_params(iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None):
+    """rt_denoise_params_init's defaults (4 passes; sigmas 1, 0.5, 0.25) with the given fields replaced."""
+    p = DenoiseParams()
+    lib().rt_denoise_params_init(C.byref(p))
+    for name, v in (("iterations", iterations), ("sigma_color", sigma_color), ("sigma_normal", sigma_normal),
+                    ("sigma_albedo", sigma_albedo)):
+        if v is not None:
+            setattr(p, name, v)
+    return p
+
+
+def denoise(canva, albedo=None, normal=None, params=None):
+    """rt_denoise_host: the built-in a-trous denoiser (rt.h; not OIDN) on host
+    (H, W, 3) float64 frames; returns the filtered canva, the inputs stay."""
+    H, W = canva.shape[:2]
+    out = np.array(canva, dtype=np.float64, order="C")
+    keep = [None if x is None else np.ascontiguousarray(x, dtype=np.float64) for x in (albedo, normal)]
+    p = params if params is not None else denoise_params()
+    check(lib().rt_denoise_host(W, H, out.ctypes.data, *[None if k is None else k.ctypes.data for k in keep],
+                                C.byref(p)))
+    return out
+
+
+def denoise_async(W, H, canva_ptr, albedo_ptr, normal_ptr, params, workspace_ptr, workspace_bytes,
+                  color3_ptr=None, stream=None):
+    """rt_denoise_async on device pointers (canva is filtered in place)."""
+    fr = Frame(canva_ptr, albedo_ptr, normal_ptr, None)
+    check(lib().rt_denoise_async(W, H, C.byref(fr), C.byref(params), workspace_ptr, workspace_bytes, color3_ptr,
+                                 stream))
+
+
+def set_denoise_atrous(enable=True, params=None):
+    """Install rt_denoise_atrous as the rt_render_rows hook (or clear the
+    hook) and set its process-wide parameters (None: the defaults)."""
+    global _hook_ref
+    check(lib().rt_set_denoise_params(None if params is None else C.byref(params)))
+    _hook_ref = C.cast(lib().rt_denoise_atrous, DENOISE_FN) if enable else DENOISE_FN()
+    lib().rt_set_denoise_hook(_hook_ref)
 
 
 def last_gather_transport():

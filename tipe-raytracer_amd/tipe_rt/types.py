@@ -49,7 +49,7 @@ RT_SKY_OFF, RT_SKY_LAST_SPHERE = 0, 1
 RT_SEM_MAIN_C, RT_SEM_CUDA = 0, 1
 RT_PREC_FP64, RT_PREC_FP32 = 0, 1
 RT_GATHER_RCCL, RT_GATHER_PEER = 0, 1
-RT_ABI_VERSION = 4
+RT_ABI_VERSION = 5
 
 
 class Vec3(C.Structure):
@@ -143,6 +143,12 @@ class Tiling(C.Structure):
 class Frame(C.Structure):
     _fields_ = [("canva", C.c_void_p), ("albedo", C.c_void_p),
                 ("normal", C.c_void_p), ("radiance", C.c_void_p)]
+
+
+class DenoiseParams(C.Structure):
+    """rt.h rt_denoise_params: the built-in a-trous denoiser (not OIDN)."""
+    _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float)]
 
 
 assert C.sizeof(Vec3) == 24 and C.sizeof(Material) == 80 and C.sizeof(Sphere) == 112
