@@ -43,7 +43,10 @@ def _slots(n):
                                                           # 11 four-row tiles, the last with one row: every
                                                           # slot has padding rows (queue kernel, table and
                                                           # register task decode)
-                                                          (3, 4, 4, "pyramid"), (3, 4, 4, "tree")])
+                                                          (3, 4, 4, "pyramid"), (3, 4, 4, "tree"),
+                                                          # two 32-row tiles for three slots: slot 2 renders
+                                                          # only padding rows (queue kernel, fixed grid)
+                                                          (3, 32, 4, "pyramid"), (3, 32, 1, "pyramid")])
 def test_render_gather_slots_bitexact(slots, tile_rows, chunks, scene):
     """tree: the C4 scene (1320-triangle BVH + AO 2.5, 8 bounces) through the
     BVH queue kernel on cyclic 1-row tiles and the gather -- C4's own

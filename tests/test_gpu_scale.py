@@ -167,7 +167,9 @@ def test_render_rows_scene_cache_tracks_content():
 def test_render_rows_two_device_slots(planes):
     """rt_init(2, {0, 0}): rt_render_rows deals cyclic 1-row tiles over two
     device slots (here both on GPU 0), copies each slot's planes back
-    asynchronously and scatters the rows; only the requested planes."""
+    asynchronously and scatters the rows; only the requested planes.  The
+    one-row band leaves the second slot without a tile: it takes no scene,
+    stream or buffer."""
     lib = tipe_rt.lib()
     devs = (C.c_int * 2)(0, 0)
     tipe_rt.check(lib.rt_init(2, devs))
@@ -177,17 +179,20 @@ def test_render_rows_two_device_slots(planes):
         for chunks in (1, 4):
             p = helpers.params(W, H, 8, 6, chunks=chunks)
             ref = helpers.oracle_render(bundle, p)
-            canva = np.full((H, W, 3), -3.0)
-            alb = np.full((H, W, 3), -3.0) if planes == "all" else None
-            nrm = np.full((H, W, 3), -3.0) if planes == "all" else None
-            tipe_rt.check(lib.rt_render_rows(C.byref(bundle.scene), C.byref(p), H - 2, 3, canva.ctypes.data,
-                                             alb.ctypes.data if alb is not None else None,
-                                             nrm.ctypes.data if nrm is not None else None))
-            assert (canva[3:H - 1] == ref["canva"][3:H - 1]).all()
-            assert (canva[:3] == -3.0).all() and (canva[H - 1:] == -3.0).all()
-            if planes == "all":
-                assert (alb[3:H - 1] == ref["albedo"][3:H - 1]).all()
-                assert (nrm[3:H - 1] == ref["normal"][3:H - 1]).all()
+            for hi, lo in ((H - 2, 3), (5, 5)):
+                canva = np.full((H, W, 3), -3.0)
+                alb = np.full((H, W, 3), -3.0) if planes == "all" else None
+                nrm = np.full((H, W, 3), -3.0) if planes == "all" else None
+                tipe_rt.check(lib.rt_render_rows(C.byref(bundle.scene), C.byref(p), hi, lo, canva.ctypes.data,
+                                                 alb.ctypes.data if alb is not None else None,
+                                                 nrm.ctypes.data if nrm is not None else None))
+                assert (canva[lo:hi + 1] == ref["canva"][lo:hi + 1]).all()
+                assert (canva[:lo] == -3.0).all() and (canva[hi + 1:] == -3.0).all()
+                if planes == "all":
+                    assert (alb[lo:hi + 1] == ref["albedo"][lo:hi + 1]).all()
+                    assert (nrm[lo:hi + 1] == ref["normal"][lo:hi + 1]).all()
+                    for a in (alb, nrm):
+                        assert (a[:lo] == -3.0).all() and (a[hi + 1:] == -3.0).all()
     finally:
         lib.rt_shutdown()
         tipe_rt.check(lib.rt_init(0, None))

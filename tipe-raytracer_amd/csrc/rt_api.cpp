@@ -1,8 +1,9 @@
 // rt_api.cpp — C-ABI of librt_hip.so (include/rt/rt.h): validation, init,
 // scene upload into the HBM layout of rt_internal.h (prepared on the host by
 // rt_scene_prep.cpp), launch descriptors and the single-device async entry
-// points.  The host-buffer drop-ins and the multi-device gather are in
-// rt_drop_in.cpp, the diagnostics in rt_diag.cpp.
+// points.  The host-buffer drop-ins are in rt_drop_in.cpp, the multi-device
+// gather in rt_gather.cpp, the denoiser's entry points in rt_denoise_api.cpp,
+// the diagnostics in rt_diag.cpp.
 // Every HIP call is checked; failures return RT_E* and set rt_last_error().
 #include <algorithm>
 #include <atomic>
@@ -110,23 +111,6 @@ int first_device(int& dev)
     const int rc = device_list(devs);
     if (rc == RT_OK) dev = devs[0];
     return rc;
-}
-
-int validate_denoise(int W, int H, const rt_denoise_params* p)
-{
-    if (W < 1 || H < 1) return fail(RT_EINVAL, "denoise: frame %dx%d", W, H);
-    if ((long long)W * H > (1ll << 30)) return fail(RT_EINVAL, "denoise: frame %dx%d above 2^30 pixels", W, H);
-    if (!p) return fail(RT_EINVAL, "denoise: params is NULL");
-    if (p->iterations < 1 || p->iterations > 8)
-        return fail(RT_EINVAL, "denoise: iterations %d outside 1..8", p->iterations);
-    const float sig[3] = {p->sigma_color, p->sigma_normal, p->sigma_albedo};
-    const char* const name[3] = {"sigma_color", "sigma_normal", "sigma_albedo"};
-    for (int i = 0; i < 3; ++i) {
-        if (!std::isfinite(sig[i])) return fail(RT_EINVAL, "denoise: %s is not finite", name[i]);
-        if (sig[i] < 0x1p-8f || sig[i] > 0x1p8f)
-            return fail(RT_EINVAL, "denoise: %s %g outside [2^-8, 2^8]", name[i], (double)sig[i]);
-    }
-    return RT_OK;
 }
 
 int validate_scene(const rt_scene* sc)
@@ -545,71 +529,6 @@ int rt_count_async(const rt_device_scene* scene, const rt_params* params, const 
     if ((rc = validate_params(params)) || (rc = validate_tiling(tiling))) return rc;
     if (!d_counters) return fail(RT_EINVAL, "d_counters is NULL");
     return launch_scene(scene, params, tiling, hip_stream, true, [&](KParams& kp) { kp.counters = d_counters; });
-}
-
-int rt_assemble_async(const rt_color* gathered, long long rank_stride, int world, int tile_rows, int rows_per_rank,
-                      int W, int H, rt_color* out, void* hip_stream)
-{
-    if (!gathered || !out) return fail(RT_EINVAL, "NULL buffer");
-    if (world < 1 || tile_rows < 1 || rows_per_rank < 0 || W < 1 || H < 1 || rows_per_rank % tile_rows ||
-        rank_stride < 0)
-        return fail(RT_EINVAL, "bad assemble geometry");
-    if (rank_stride == 0) rank_stride = (long long)rows_per_rank * W;
-    if (rank_stride < (long long)rows_per_rank * W) return fail(RT_EINVAL, "rank_stride overlaps rank blocks");
-    const long long tiles = (H + tile_rows - 1) / tile_rows;
-    if ((long long)world * (rows_per_rank / tile_rows) < tiles)
-        return fail(RT_EINVAL, "gather holds %d tiles/rank x %d ranks < %lld tiles", rows_per_rank / tile_rows,
-                    world, tiles);
-    const int e = launch_assemble((const double*)gathered, rank_stride, world, tile_rows, rows_per_rank, W, H,
-                                  (double*)out, hip_stream);
-    if (e) return fail(RT_EDEVICE, "assemble launch: %s", hipGetErrorString((hipError_t)e));
-    return RT_OK;
-}
-
-int rt_denoise_pack_async(int W, int H, const rt_frame* frame, float* color3, float* albedo3, float* normal3,
-                          void* hip_stream)
-{
-    if (W < 1 || H < 1 || !frame || !frame->canva || !color3)
-        return fail(RT_EINVAL, "bad denoise_pack_async arguments");
-    const int e = launch_denoise_pack((long long)W * H, (const double*)frame->canva,
-                                      albedo3 ? (const double*)frame->albedo : nullptr,
-                                      normal3 ? (const double*)frame->normal : nullptr, color3, albedo3, normal3,
-                                      hip_stream);
-    if (e) return fail(RT_EDEVICE, "denoise pack launch: %s", hipGetErrorString((hipError_t)e));
-    return RT_OK;
-}
-
-void rt_denoise_params_init(rt_denoise_params* p)
-{
-    if (!p) return;
-    p->iterations = 4;
-    p->sigma_color = 1.0f;
-    p->sigma_normal = 0.5f;
-    p->sigma_albedo = 0.25f;
-}
-
-size_t rt_denoise_workspace_bytes(int W, int H)
-{
-    if (W < 1 || H < 1 || (long long)W * H > (1ll << 30)) return 0;
-    return 4 * denoise_plane_floats((long long)W * H) * sizeof(float);
-}
-
-int rt_denoise_async(int W, int H, const rt_frame* frame, const rt_denoise_params* params, void* workspace,
-                     size_t workspace_bytes, float* color3_out, void* hip_stream)
-{
-    const int rc = validate_denoise(W, H, params);
-    if (rc) return rc;
-    if (!frame || !frame->canva) return fail(RT_EINVAL, "denoise: canva is NULL");
-    if (!workspace) return fail(RT_EINVAL, "denoise: workspace is NULL");
-    if ((uintptr_t)workspace % 16) return fail(RT_EINVAL, "denoise: workspace is not 16-byte aligned");
-    if (workspace_bytes < rt_denoise_workspace_bytes(W, H))
-        return fail(RT_EINVAL, "denoise: workspace of %zu bytes, %dx%d needs %zu", workspace_bytes, W, H,
-                    rt_denoise_workspace_bytes(W, H));
-    const int e = launch_denoise(W, H, (double*)frame->canva, (const double*)frame->albedo,
-                                 (const double*)frame->normal, params->iterations, params->sigma_color,
-                                 params->sigma_normal, params->sigma_albedo, (float*)workspace, color3_out, hip_stream);
-    if (e) return fail(RT_EDEVICE, "denoise launch: %s", hipGetErrorString((hipError_t)e));
-    return RT_OK;
 }
 
 }  // extern "C"

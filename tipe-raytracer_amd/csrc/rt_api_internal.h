@@ -1,6 +1,7 @@
 // rt_api_internal.h — what the C-ABI's files (rt_api.cpp, rt_drop_in.cpp,
-// rt_diag.cpp) share: error reporting, the device list, owning device memory
-// and the uploaded scene.
+// rt_gather.cpp, rt_denoise_api.cpp, rt_diag.cpp) share: error reporting, the
+// device list, owning device memory and the uploaded scene.  What a drop-in
+// holds while it runs (streams, buffers, slots) is in rt_host_slots.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,7 +65,6 @@ int first_device(int& dev);
 
 int validate_scene(const rt_scene* sc);
 int validate_params(const rt_params* p);
-int validate_denoise(int W, int H, const rt_denoise_params* p);   // frame size and parameters of the built-in denoiser
 
 void make_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling* t, KParams& kp, double* uni);
 int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count);
