@@ -378,8 +378,8 @@ enum {
     RT_CNT_BVH_STACK_OVER, /* BVH stack pushes made at a depth >= the LDS
                              stack of the kernel a render of the same params
                              takes (the queue kernel's 24 / 32 / 14 entries,
-                             else the fixed grid's 48; rt_kernels.hip
-                             choose_render).  Must be 0: the host admits a
+                             else the fixed grid's 48; rt_launch_plan.cpp
+                             plan_render).  Must be 0: the host admits a
                              tree by its exact stack bound (rt_bvh.cpp); a
                              nonzero count means that bound is wrong (GPU
                              diagnostic, rt_count_async only).  The

@@ -22,7 +22,7 @@ from tipe_rt import scenes
 from test_bvh_pack import mesh_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-K_STACK_Q = 24          # rt_triangles.h kStackQ
+K_STACK_Q = 24          # rt_bvh.h kStackQ
 K_STACK4 = 48           # rt_bvh.h kStack4 (the fixed-grid kernel's stacks)
 
 

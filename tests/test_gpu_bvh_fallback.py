@@ -56,26 +56,43 @@ def render_and_compare(bundle, p):
     return kernel
 
 
+def deep_far_scene():
+    return helpers.SceneBundle(scenes.cornell_spheres(),
+                               with_far_triangle(scenes.moved(scenes.load_tree_fixture(), scenes.TREE_MOVE)))
+
+
+def shallow_far_scene():
+    sph, mesh = scenes.synthetic_cornell(10, 100)
+    return helpers.SceneBundle(sph, with_far_triangle(mesh))
+
+
+# scene, params, kernel (tests/test_launch_plan.py checks the same triples on the CPU)
+FALLBACK = {
+    "deep_far": (deep_far_scene, lambda: helpers.params(40, 30, 6, 8, use_ao=True, chunks=4), "render_kernel<BVH>"),
+    "deep": (helpers.tree_scene, lambda: helpers.params(40, 30, 6, 8, use_ao=True, chunks=4),
+             "render_kernel_q<QB=3,OP>"),
+    "shallow_far": (shallow_far_scene, lambda: helpers.params(48, 36, 8, 6, chunks=4), "render_kernel_q<QB=4>"),
+}
+
+
+def fallback_case(name):
+    scene, params, kernel = FALLBACK[name]
+    assert render_and_compare(scene(), params()) == kernel
+
+
 def test_deep_tree_without_binary16_nodes_takes_fixed_grid():
-    bundle = helpers.SceneBundle(scenes.cornell_spheres(),
-                                 with_far_triangle(scenes.moved(scenes.load_tree_fixture(), scenes.TREE_MOVE)))
-    p = helpers.params(40, 30, 6, 8, use_ao=True, chunks=4)
-    assert render_and_compare(bundle, p) == "render_kernel<BVH>"
+    fallback_case("deep_far")
 
 
 def test_deep_tree_with_binary16_nodes_takes_queue_qb3():
     """Control: the same tree without the far triangle packs, and runs the
     deep-tree queue kernel (its opaque-material instantiation: the tree's
     texels and the README spheres are opaque, test_gpu_instantiations.py)."""
-    p = helpers.params(40, 30, 6, 8, use_ao=True, chunks=4)
-    assert render_and_compare(helpers.tree_scene(), p) == "render_kernel_q<QB=3,OP>"
+    fallback_case("deep")
 
 
 def test_shallow_tree_without_binary16_nodes_keeps_queue_qb4():
-    sph, mesh = scenes.synthetic_cornell(10, 100)
-    bundle = helpers.SceneBundle(sph, with_far_triangle(mesh))
-    p = helpers.params(48, 36, 8, 6, chunks=4)
-    assert render_and_compare(bundle, p) == "render_kernel_q<QB=4>"
+    fallback_case("shallow_far")
 
 
 def test_far_triangle_is_invisible():

@@ -9,7 +9,7 @@ r04 splits render_kernel_q by what the scene can reach (DESIGN §4a
   * QB = 3 with OPQ: the deep-tree kernel when every sphere material, every
     texel and every material index (no 3 or 4, tri_material's overrides)
     is opaque (C4).
-The host picks them (rt_kernels.hip launch_render) from the scene upload's
+The host picks them (rt_launch_plan.cpp plan_render) from the scene upload's
 material flags.  main.c:196-234 decides per hit: alpha < 0.0001 is a hole,
 alpha <= 0.99 refracts, anything else (NaN included) shades; the opaque
 gate is exactly "no material takes either of the first two branches", so a
@@ -42,17 +42,23 @@ def prm(**kw):
     return helpers.params(q["W"], q["H"], q["spp"], q["bounces"], chunks=4)
 
 
+# alpha of the extra sphere -> the kernel (tests/test_launch_plan.py checks the same pairs on the CPU)
+ALPHA_KERNEL = {0.5: "render_kernel_q<QB=-1>", 0.99: "render_kernel_q<QB=-1>", 0.00005: "render_kernel_q<QB=-1>",
+                0.0: "render_kernel_q<QB=-1>", 0.9900001: "render_kernel_q<QB=-2>"}
+OVERRIDE_KERNEL = "render_kernel_q<QB=3>"
+
+
 def test_opaque_sphere_scene_takes_qb_minus2():
     assert render_and_compare(helpers.cornell(), prm()) == "render_kernel_q<QB=-2>"
 
 
 @pytest.mark.parametrize("alpha", [0.5, 0.99, 0.00005, 0.0])
 def test_transparent_or_hole_sphere_takes_qb_minus1(alpha):
-    assert render_and_compare(one_transparent(alpha), prm()) == "render_kernel_q<QB=-1>"
+    assert render_and_compare(one_transparent(alpha), prm()) == ALPHA_KERNEL[alpha]
 
 
 def test_alpha_just_above_refraction_threshold_is_opaque():
-    assert render_and_compare(one_transparent(0.9900001), prm()) == "render_kernel_q<QB=-2>"
+    assert render_and_compare(one_transparent(0.9900001), prm()) == ALPHA_KERNEL[0.9900001]
 
 
 def test_whole_box_transparent_takes_qb_minus1():
@@ -78,8 +84,7 @@ def test_tree_scene_with_transparent_sphere_keeps_qb3():
     assert render_and_compare(bundle, p) == "render_kernel_q<QB=3>"
 
 
-@pytest.mark.parametrize("mat_index", [3, 4])
-def test_tree_with_override_material_keeps_qb3(mat_index):
+def override_tree(mat_index):
     """tri_material's material indices 3 and 4 force alpha 0.1 / 0.6 whatever
     the texel holds: a tree whose first triangles use one of them is not
     opaque.  The texel table gets entries up to that index (copies of
@@ -92,15 +97,19 @@ def test_tree_with_override_material_keeps_qb3(mat_index):
         mats2[k] = mats[k] if k < nm * tw * th else mats[0]
     for k in range(0, len(tris), 7):
         qm[k] = mat_index
-    bundle = helpers.SceneBundle(scenes.cornell_spheres(), (tris, qm, mats2, tw, th, n_new))
+    return helpers.SceneBundle(scenes.cornell_spheres(), (tris, qm, mats2, tw, th, n_new))
+
+
+@pytest.mark.parametrize("mat_index", [3, 4])
+def test_tree_with_override_material_keeps_qb3(mat_index):
     p = helpers.params(40, 30, 6, 8, use_ao=True, chunks=4)
-    assert render_and_compare(bundle, p) == "render_kernel_q<QB=3>"
+    assert render_and_compare(override_tree(mat_index), p) == OVERRIDE_KERNEL
 
 
 @pytest.mark.parametrize("scene", ["tree", "sweep", "mineways", "nature", "main_regime"])
 def test_bvh_stack_bound_holds_on_the_gpu(scene):
     """rt_count_async checks every BVH push against the LDS stack of the
-    kernel launch_render picks for the tree (rt.h RT_CNT_BVH_STACK_OVER):
+    kernel plan_render picks for the tree (rt.h RT_CNT_BVH_STACK_OVER):
     the C4 tree (deep-tree queue kernel, 24 entries), the 100-triangle sweep
     mesh and mineways (606 triangles), over a whole frame with AO."""
     from test_gpu_parity import assert_stack_bound_holds

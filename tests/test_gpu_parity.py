@@ -253,7 +253,7 @@ def test_cornell_spp_chunks_bitexact():
 
 def test_spp_chunks_row_bands(monkeypatch):
     """A partial-sum budget smaller than the frame splits the launch into
-    16-row bands reusing one buffer (rt_api.cpp launch_on_stream): same image."""
+    16-row bands reusing one buffer (rt_launch_plan.cpp plan_render): same image."""
     monkeypatch.setenv("RT_PARTIAL_BUDGET", str(16 * 37 * 4 * 72))     # 16 rows of 37 px x 4 chunks
     check_parity(helpers.cornell(), helpers.params(37, 53, 8, 5, chunks=4))
 

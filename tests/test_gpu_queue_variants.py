@@ -2,7 +2,7 @@
 off/on x AO off/on = 24 kernels (rt_kernels.hip with_queue_variant).
 
 The host maps (qb, opq, sky, ao) to the instantiation in one place; each
-case here renders a scene that choose_render sends to one of them, checks
+case here renders a scene that plan_render sends to one of them, checks
 rt_last_render_kernel's name and compares all four planes with the oracle
 bit for bit.  The sky halves use sky_scene()'s enclosing sky sphere (the
 last sphere, main.c:64-71) and texels with sky_mode 1.
@@ -55,12 +55,15 @@ def bundle_of(extra, mesh, sky):
     return helpers.SceneBundle(sph, mesh, sky=sk.sky)
 
 
+def variant_params(sky, ao):
+    return helpers.params(24, 18, 4, 6, use_ao=ao, ao=2.5, chunks=2, sky_mode=1 if sky else 0)
+
+
 @pytest.mark.parametrize("ao", [False, True], ids=["noao", "ao"])
 @pytest.mark.parametrize("sky", [False, True], ids=["nosky", "sky"])
 @pytest.mark.parametrize("variant", list(VARIANTS))
 def test_queue_variant(variant, sky, ao):
     name, extra, mesh = VARIANTS[variant]
     bundle = bundle_of(extra, mesh(), sky)
-    p = helpers.params(24, 18, 4, 6, use_ao=ao, ao=2.5, chunks=2, sky_mode=1 if sky else 0)
-    kernel = render_and_compare(bundle, p)
+    kernel = render_and_compare(bundle, variant_params(sky, ao))
     assert kernel == name

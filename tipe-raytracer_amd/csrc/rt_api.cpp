@@ -1,16 +1,13 @@
 // rt_api.cpp — C-ABI of librt_hip.so (include/rt/rt.h): validation, init,
 // scene upload into the HBM layout of rt_internal.h (prepared on the host by
-// rt_scene_prep.cpp), launch descriptors and the single-device async entry
-// points.  The host-buffer drop-ins are in rt_drop_in.cpp, the multi-device
-// gather in rt_gather.cpp, the denoiser's entry points in rt_denoise_api.cpp,
+// rt_scene_prep.cpp), launches (descriptor and plan: rt_launch_plan.cpp) and
+// the single-device async entry points.  The host-buffer drop-ins are in
+// rt_drop_in.cpp, the multi-device gather in rt_gather.cpp, the denoiser's entry points in rt_denoise_api.cpp,
 // the diagnostics in rt_diag.cpp.
 // Every HIP call is checked; failures return RT_E* and set rt_last_error().
-#include <algorithm>
 #include <atomic>
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -41,41 +38,12 @@ int validate_tiling(const rt_tiling* t)
     return RT_OK;
 }
 
-void set_tiling(KParams& kp, const rt_tiling* t, int H)
-{
-    kp.row_base = t->row_base;
-    kp.tile_rows = t->tile_rows;
-    kp.tile_first = t->tile_first;
-    kp.tile_step = t->tile_step;
-    kp.n_tiles = t->n_tiles;
-    kp.row_end = H;
-    kp.local_rows = t->n_tiles * t->tile_rows;
-}
-
 void set_frame(KParams& kp, const rt_frame* frame)
 {
     kp.canva = (double*)frame->canva;
     kp.albedo = (double*)frame->albedo;
     kp.normal = (double*)frame->normal;
     kp.radiance = (double*)frame->radiance;
-}
-
-// With spp_chunks > 1 the per-chunk partial sums ([chunks][rows*W][9]
-// doubles) are bounded by a budget of bytes per launch: taller frames are
-// rendered in row bands that reuse one partial buffer (pixels are
-// independent, so banding does not change any result).
-size_t partial_row_bytes(const KParams& kp) { return (size_t)kp.chunks * kp.W * 9 * sizeof(double); }
-
-// Rows per launch of a render of kp (RT_PARTIAL_BUDGET overrides the 4 GiB
-// budget; tests use a small one to exercise the banding).
-int render_band_rows(const KParams& kp)
-{
-    if (kp.chunks <= 1) return kp.local_rows;
-    const char* e = std::getenv("RT_PARTIAL_BUDGET");
-    const long long v = e ? std::atoll(e) : 0;
-    const size_t budget = v > 0 ? (size_t)v : ((size_t)4 << 30);
-    const size_t rows = std::max<size_t>(16, budget / partial_row_bytes(kp) / 16 * 16);
-    return (int)std::min<size_t>(rows, (size_t)kp.local_rows);
 }
 
 }  // namespace
@@ -171,136 +139,13 @@ void free_scene(rt_device_scene* s)
     delete s;
 }
 
-void make_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling* t, KParams& kp, double* uni)
+void fill_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling* t, KParams& kp, double* uni)
 {
-    const SceneFacts& f = sc->facts;
-    std::memset(&kp, 0, sizeof kp);
-    kp.sph = sc->sph;
-    kp.sph_cand = sc->sph_cand;
-    kp.cand_lmax = f.cand_lmax;
-    kp.sph_mat = sc->sph_mat;
-    kp.tri = sc->tri;
-    kp.tri_tex = sc->tri_tex;
-    kp.tri_uv = sc->tri_uv;
-    kp.texels = sc->texels;
-    kp.tri_orig = sc->tri_orig;
-    kp.sph_rinv = sc->sph_rinv;
-    kp.sph_disp = sc->sph_disp;
-    kp.tri_mat = sc->tri_mat;
-    kp.cuda = p->semantics == RT_SEM_CUDA ? 1 : 0;
-    for (int i = 0; i < 6; ++i) kp.cbb[i] = f.cbb[i];
-    if (p->sky_mode == RT_SKY_LAST_SPHERE && sc->sky && f.ns > 0) {
-        kp.sky = sc->sky;
-        kp.sky_w = f.sky_w;
-        kp.sky_h = f.sky_h;
-    }
-    kp.ns = f.ns;
-    kp.ns_pad = f.ns_pad;
-    kp.ns_cand = std::isfinite(f.cand_lmax) ? f.ns_pad : 0;
-    kp.cand_orig = sc->cand_orig;
-    kp.sph_slot = sc->sph_slot;
-    kp.ns_merge = f.ns_merge;
-    kp.ns_fwd = f.ns_fwd;
-    kp.nt = f.nt;
-    kp.tw = f.tw;
-    kp.th = f.th;
-    kp.n_texels = f.n_texels;
-    kp.W = p->largeur_image;
-    kp.H = p->hauteur_image;
-    kp.S = p->nbRayonParPixel;
-    kp.B = p->nbRebondMax;
-    for (int i = 0; i < 3; ++i) {
-        uni[U_CAM_O + i] = p->cam.origin.e[i];
-        uni[U_CAM_H + i] = p->cam.horizontal.e[i];
-        uni[U_CAM_V + i] = p->cam.vertical.e[i];
-        uni[U_CAM_C + i] = p->cam.coin_bas_gauche.e[i];
-    }
-    double focus = p->focus_distance, ox = p->ouverture_x, oy = p->ouverture_y, AO = p->AO_intensity;
-    if (p->compat_int_truncation && p->semantics != RT_SEM_CUDA) {   // ThreadData int fields, main.c:42-43
-        focus = (double)(int)focus;
-        ox = (double)(int)ox;
-        oy = (double)(int)oy;
-        AO = (double)(int)AO;
-    }
-    uni[U_FOCUS] = focus;
-    uni[U_OX] = ox;
-    uni[U_OY] = oy;
-    // camera.h:49-54: the ray starts at origin + (jx*ox, jy*oy, 0); with ox = oy = 0
-    // the offsets are +-0 and the sum is the origin itself unless a coordinate is -0
-    kp.cam_pin = ox == 0.0 && oy == 0.0 && !(p->cam.origin.e[0] == 0.0 && std::signbit(p->cam.origin.e[0])) &&
-                 !(p->cam.origin.e[1] == 0.0 && std::signbit(p->cam.origin.e[1])) &&
-                 !(p->cam.origin.e[2] == 0.0 && std::signbit(p->cam.origin.e[2]));
-    kp.opaque = f.sph_opaque ? 1 : 0;
-    kp.opaque_all = f.sph_opaque && (f.nt == 0 || f.tri_opaque) ? 1 : 0;
-    uni[U_AO] = AO;
-    uni[U_WM1] = (double)(p->largeur_image - 1);    // main.c:265 (largeur_image-1)
-    uni[U_HM1] = (double)(p->hauteur_image - 1);
-    uni[U_RC_WM1] = uni[U_RC_HM1] = 0.0;            // refined on the device (set_uniforms_kernel)
-    kp.useAO = p->useAO ? 1 : 0;
-    kp.key0 = (uint32_t)p->seed;
-    kp.key1 = (uint32_t)(p->seed >> 32);
-    kp.chunks = rt_resolve_spp_chunks(p->spp_chunks, p->nbRayonParPixel);
-    kp.chunk_taper = rt_chunk_taper_levels(kp.S, kp.chunks);      // rt.h rt_chunk_bound
-    kp.chunk_den = kp.chunk_taper ? (unsigned)(kp.chunks - kp.chunk_taper) * (1u << kp.chunk_taper) +
-                                        ((1u << kp.chunk_taper) - 1u)
-                                  : (unsigned)kp.chunks;
-    set_tiling(kp, t, p->hauteur_image);
-    // The BVH padding assumed every ray origin within r_scene (rt_bvh.cpp);
-    // primary rays start at the camera origin + (dx, dy, 0), |dx| <= |ox|/2.
-    double cam = 0.0;
-    for (int i = 0; i < 3; ++i) cam = std::max(cam, std::fabs(p->cam.origin.e[i]));
-    cam += 0.5 * (std::fabs(ox) + std::fabs(oy));
-    if (!std::isfinite(cam) || !std::isfinite(p->cam.origin.e[0]) || !std::isfinite(p->cam.origin.e[1]) ||
-        !std::isfinite(p->cam.origin.e[2]))
-        cam = HUGE_VAL;                  // std::max drops NaN: no gate below may pass on a NaN camera
-    // Zero-throughput exit (rt_fixed_grid.h LanePath::zero_rc): exact when the
-    // shading values are bounded and, with AO, the AO factor stays finite.
-    kp.zero_exit = g_zero_exit.load() && p->semantics != RT_SEM_CUDA && f.mats_bounded &&
-                   (!kp.useAO || (AO > 0.0 && AO <= 1000.0 && std::fmax(f.coord_max, cam) <= 0x1p20));
-    // TriTex::tex0 (constant texels of uv-less triangles): a hit point P is then
-    // within ~2^101 of the origin, the signed areas of get_barycentric_coord stay
-    // below 2^205 and areaABC >= |N| (1 - 2^-50) with |N| >= 1e-6 / |d| for any
-    // hit (det >= 1e-6), so the barycentrics are finite and u = v = +-0
-    kp.tex_const = f.all_tex0 && std::fmax(f.coord_max, cam) <= 0x1p100;
-    // (origins beyond r_scene -- the camera, hit points on far spheres -- widen
-    // the walk's margins per ray, rt_triangles.h ray32; a non-finite camera
-    // takes the every-triangle scan)
-    if (sc->bvh && p->accel == RT_ACCEL_AUTO && std::isfinite(cam)) {
-        kp.bvh = sc->bvh;
-        kp.bvhh = sc->bvhh;
-        kp.bvh_srel = f.s_rel;
-        kp.bvh_sabs = f.s_abs;
-        kp.bvh_rb = f.r_scene;
-        kp.bvh_kdelta = f.k_delta;
-        {
-            float rf = (float)f.r_scene;              // rb_f (1 + 2^-23) <= R_b
-            while (rf > 0.0f && (double)rf * (1.0 + 0x1p-23) > f.r_scene) rf = std::nextafter(rf, 0.0f);
-            kp.bvh_rb_f = rf;
-            // origins: the camera (+ aperture), hit points on the spheres and on
-            // the triangles (inside R_b by construction)
-            kp.bvh_far = !(cam <= f.r_scene && f.sph_bound <= f.r_scene);
-        }
-        kp.bvh_rbox = f.bvh_rbox;
-        // the traversal stack's uint16 entries (node indices): entries the tree can
-        // need (rt_bvh.cpp's exact bound), or more than any stack when an index
-        // would not fit
-        kp.bvh_stack = (f.bvh_nodes < 0x8000 && f.nt <= 0x8000) ? f.bvh_stack4 : 1 << 30;
-        // a wide tree (rt_bvh.h): 32-bit stacks and the wide 64-byte nodes, so
-        // its exact bound always counts; it has no BvhNodeH form
-        if (f.bvh_wide) {
-            kp.bvh_wide = 1;
-            kp.bvhw = sc->bvhw;
-            kp.bvh_stack = f.bvh_stack4;
-        }
-        // shallow trees finish most walks in one round with 4 visits; deeper ones
-        // do best with 3 (measured: sweep depth4 3: 3395 -> 3542 at 4; C4 depth4 7:
-        // 1134 at 3, 1122 at 4)
-        kp.bvh_steps = f.bvh_depth <= 4 ? 4 : 3;
-        kp.bvh_nodes = f.bvh_nodes;
-    }
+    fill_kparams(*sc, sc->facts, p, t, g_zero_exit.load() != 0, kp, uni);
 }
 
-// Stream-ordered scratch (uniform block, chunk partials) around one launch.
+// One render or count run of kp as plan_render lays it out, with its stream-
+// ordered scratch (uniform block, the chunk partials of one band).
 // The device's default memory pool keeps freed blocks (release threshold
 // raised once), so repeated launches do not re-map memory.
 int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count)
@@ -317,6 +162,7 @@ int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count)
             }
         });
     }
+    const RenderPlan plan = plan_render(kp, count);     // kernel, stack and bands, decided once
     double* d_uni = nullptr;
     double* d_part = nullptr;
     // uniform block + render_kernel_q's task counter (on its own 64-byte line)
@@ -324,23 +170,15 @@ int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count)
     UniBlock ub;
     for (int i = 0; i < U_COUNT; ++i) ub.v[i] = uni[i];
     hipError_t e = (hipError_t)launch_set_uniforms(ub, d_uni, st);
-    // a count run is one band without partials; it asks for the render's band
-    // only to find out whether that render has the task counter
-    const int band_r = render_band_rows(kp);
-    const int band = count ? kp.local_rows : band_r;
-    if (kp.chunks > 1 && !count && e == hipSuccess)
-        e = hipMallocAsync((void**)&d_part, partial_row_bytes(kp) * band, st);
+    if (plan.partial_bytes && e == hipSuccess) e = hipMallocAsync((void**)&d_part, plan.partial_bytes, st);
     kp.uni = d_uni;
     kp.partial = d_part;
-    // the queue kernel numbers tasks (chunk, pixel of the band) in 32 bits
-    const bool task_ok = kp.chunks > 1 && (unsigned long long)band_r * kp.W * kp.chunks < (1ull << 31);
-    kp.task_ctr = (d_part && task_ok) ? (unsigned*)(d_uni + ((U_COUNT + 7) / 8 + 1) * 8) : nullptr;
-    // the stack of the kernel a render of these params takes
-    kp.stack_cap = choose_render(kp, count ? task_ok : kp.task_ctr != nullptr).stack_cap;
-    for (int y0 = 0; e == hipSuccess && y0 < kp.local_rows; y0 += band) {
+    kp.task_ctr = (d_part && plan.task_ok) ? (unsigned*)(d_uni + ((U_COUNT + 7) / 8 + 1) * 8) : nullptr;
+    kp.stack_cap = plan.stack_cap;
+    kp.band_rows = plan.band_rows;
+    for (int y0 = 0; e == hipSuccess && y0 < kp.local_rows; y0 += plan.band_rows) {
         kp.band_y0 = y0;
-        kp.band_rows = band;
-        e = (hipError_t)(count ? launch_count(kp, st) : launch_render(kp, st));
+        e = (hipError_t)(count ? launch_count(kp, plan, st) : launch_render(kp, plan, st));
     }
     if (d_part) (void)hipFreeAsync(d_part, st);
     (void)hipFreeAsync(d_uni, st);
@@ -356,7 +194,7 @@ int launch_scene(const rt_device_scene* scene, const rt_params* params, const rt
 {
     KParams kp;
     double uni[U_COUNT];
-    make_kparams(scene, params, tiling, kp, uni);
+    fill_kparams(scene, params, tiling, kp, uni);
     set(kp);
     if (kp.local_rows == 0) return RT_OK;      // (validate_params: W >= 1)
     DeviceGuard guard(scene->device);

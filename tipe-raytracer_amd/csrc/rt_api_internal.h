@@ -9,6 +9,7 @@
 
 #include "rt/rt.h"
 #include "rt_internal.h"
+#include "rt_launch_plan.h"
 #include "rt_scene_prep.h"
 
 namespace rt {
@@ -66,7 +67,9 @@ int first_device(int& dev);
 int validate_scene(const rt_scene* sc);
 int validate_params(const rt_params* p);
 
-void make_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling* t, KParams& kp, double* uni);
+// rt_launch_plan.h's fill_kparams on an uploaded scene, with rt_set_zero_throughput_exit's switch;
+// launch_on_stream plans the launch (plan_render) and runs its bands.
+void fill_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling* t, KParams& kp, double* uni);
 int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count);
 void free_scene(rt_device_scene* s);
 

@@ -9,7 +9,7 @@ namespace rt {
 
 constexpr int kMaxDepth = 30;       // binary build depth cap (leaves below it hold several triangles); the
                                     // kernels admit a tree by its exact stack bound (BvhBuild::stack4 vs
-                                    // kStack4 / kStackQ / kStackQ4), not by its depth
+                                    // kStack4 and the kStackQ* below), not by its depth
 
 // One internal node: the padded boxes of both children (one 64-byte fetch
 // per visit).  Bounds are the padded double boxes rounded OUTWARD to float
@@ -36,6 +36,9 @@ struct BvhNode4 {
 static_assert(sizeof(BvhNode4) == 128, "BvhNode4");
 
 constexpr int kStack4 = 48;         // kernel LDS stack entries (3 pushes per 4-wide level)
+// ... and of the queue kernel's instantiations (rt_triangles.h bvh_stack_q, bvh_stack_qw): QB 3 with every
+// material opaque, QB 3, QB 4, QB 5.  plan_render (rt_launch_plan.cpp) admits a tree by its exact bound.
+constexpr int kStackQ = 24, kStackQN = 32, kStackQ4 = 14, kStackQW = 32;
 
 // The same 4-wide node in 64 bytes for the queue kernel (r03): binary16
 // planes relative to a binary16 node origin, rounded outward, so that

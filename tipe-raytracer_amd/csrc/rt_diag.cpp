@@ -1,6 +1,5 @@
 // rt_diag.cpp — the C-ABI's diagnostics: rt_selftest_math and the
 // rt_verify_* counters (rt_verify.h kernels), each on the first rt_init device.
-#include <cstring>
 #include <memory>
 
 #include "rt_api_internal.h"
@@ -61,18 +60,8 @@ int rt_verify_sphere_pass(const rt_scene* scene, const double* rays, long long n
     if ((rc = rt_scene_upload(dev, scene, &raw))) return rc;
     ScenePtr ds(raw, free_scene);
     DeviceGuard guard(dev);
-    KParams kp;
-    std::memset(&kp, 0, sizeof kp);
-    kp.sph = ds->sph;
-    kp.sph_cand = ds->sph_cand;
-    kp.cand_lmax = ds->facts.cand_lmax;
-    kp.ns = ds->facts.ns;
-    kp.ns_pad = ds->facts.ns_pad;
-    kp.ns_cand = std::isfinite(ds->facts.cand_lmax) ? ds->facts.ns_pad : 0;
-    kp.cand_orig = ds->cand_orig;
-    kp.sph_slot = ds->sph_slot;
-    kp.ns_merge = ds->facts.ns_merge;
-    kp.ns_fwd = ds->facts.ns_fwd;
+    KParams kp = {};
+    set_sphere_fields(kp, *ds, ds->facts);
     DevArray<double> d_rays;
     hipError_t e = d_rays.upload(rays, (size_t)n * 6);
     if (e == hipSuccess) e = run_counted(counts, [&](u64* d) { return launch_verify_spheres(kp, d_rays, n, d); });
@@ -98,14 +87,8 @@ int rt_verify_texel_map(const rt_scene* scene, const double* pts, const int* tri
     if (!ds->tri_uv)
         return fail(RT_EUNSUPPORTED, "verify_texel_map: the scene has no affine texel map (every uv 0)");
     DeviceGuard guard(dev);
-    KParams kp;
-    std::memset(&kp, 0, sizeof kp);
-    kp.tri = ds->tri;
-    kp.tri_tex = ds->tri_tex;
-    kp.tri_uv = ds->tri_uv;
-    kp.tw = ds->facts.tw;
-    kp.th = ds->facts.th;
-    kp.n_texels = ds->facts.n_texels;
+    KParams kp = {};
+    set_triangle_fields(kp, *ds, ds->facts);
     DevArray<double> d_pts;
     DevArray<int> d_tri;
     hipError_t e = d_pts.upload(pts, (size_t)n * 3);

@@ -167,7 +167,7 @@ int RenderSlot::render(int device, const rt_scene* scene, const rt_params* param
     if (e != hipSuccess) return fail(RT_EDEVICE, "device %d frame: %s", device, hipGetErrorString(e));
     KParams kp;
     double uni[U_COUNT];
-    make_kparams(sc.get(), params, &t, kp, uni);
+    fill_kparams(sc.get(), params, &t, kp, uni);
     kp.row_end = row_end;
     double* next = (double*)buf.p;
     double** dst[4] = {&kp.canva, &kp.albedo, &kp.normal, &kp.radiance};

@@ -1,6 +1,7 @@
 // rt_internal.h — device-side scene layout and launch descriptors shared by
-// the C-ABI (rt_api.cpp; the scene's arrays are made by rt_scene_prep.cpp) and
-// the kernels (rt_kernels.hip and the headers it includes).
+// the C-ABI (rt_api.cpp; the scene's arrays are made by rt_scene_prep.cpp, the
+// descriptor and the launch plan by rt_launch_plan.cpp) and the kernels
+// (rt_kernels.hip and the headers it includes).
 //
 // HBM layout of one uploaded scene (DESIGN.md "Data layout"):
 //   SphCand [ns_pad] 32 B  center, |C|^2 - radius^2 — the candidate pass,
@@ -116,8 +117,9 @@ struct KParams {
     int sky_w, sky_h;
     double bvh_srel, bvh_sabs;   // distance-cull slack (rt_bvh.cpp)
     float bvh_rbox;              // >= |every bound| of the tree's boxes (single-precision slab margin)
-    int bvh_stack;               // traversal stack entries the tree can need (rt_bvh.h BvhBuild::stack4)
-    int bvh_steps;               // queue kernel: node visits per lane and round (host: by tree depth)
+    int bvh_stack;               // host only (plan_render): stack entries the tree can need (BvhBuild::stack4),
+                                 // 1 << 30 when a narrow tree's node index does not fit 16 bits
+    int bvh_steps;               // host only (plan_render): 4 for a tree of 4-wide depth <= 4, else 3
     int bvh_nodes;               // 4-wide nodes (breadth-first order: the top levels first)
     int ns, ns_pad, nt;
     int tw, th;
@@ -152,16 +154,16 @@ struct KParams {
                                                  // chunks (udiv_q); qm_chunks 0: 64-bit chunk starts
     unsigned long long* trace;   // render_kernel_q diagnostics (RT_QUEUE_TRACE), normally null
     unsigned long long* counters;
-    int opaque;              // every sphere material opaque: !(alpha < 0.0001) && !(alpha <= 0.99) (no hole,
-                             // no refraction; the queue kernel's QB = -2 instantiation).  Last, so the
-                             // other fields keep their kernarg offsets (and the kernels their SMEM loads)
-    int opaque_all;          // ... and so is every triangle material: every texel, no material index 3 or 4
-                             // (tri_material's alpha overrides); the deep-tree OPQ instantiation
+    int opaque;              // host only (plan_render: QB -2): every sphere material opaque, !(alpha < 0.0001)
+                             // && !(alpha <= 0.99) (no hole, no refraction).  Last, so the other fields
+                             // keep their kernarg offsets (and the kernels their SMEM loads)
+    int opaque_all;          // host only (plan_render: OPQ): ... and so is every triangle material: every
+                             // texel, no material index 3 or 4 (tri_material's alpha overrides)
     int ns_cand;             // spheres the candidate pass scans: ns_pad, or 0 when cand_lmax is +inf (every
                              // ray then takes the exact scan: non-finite spheres, or more than 65534
                              // spheres, whose slots do not fit cand_tag's 16 bits)
-    int stack_cap;           // BVH stack entries of the kernel launch_render picks for this launch
-                             // (choose_render; host-set): what COUNT runs check pushes against
+    int stack_cap;           // COUNT runs only: BVH stack entries of the kernel a render of these params
+                             // takes (RenderPlan::stack_cap), which they check every push against
     double bvh_rb;           // the origin bound R_b the tree's padding assumed (rt_bvh.h r_scene)
     double bvh_kdelta;       // padding growth per unit of origin beyond it (rt_bvh.h k_delta)
     float bvh_rb_f;          // a float with rb_f (1 + 2^-23) <= R_b (the walk's cheap "inside" test)
@@ -173,25 +175,17 @@ struct KParams {
     const int* cand_orig;    // [ns_pad] candidate record (slot) j describes sphere cand_orig[j] of sph
     const SphGeo* sph_slot;  // [ns_pad] sph[cand_orig[j]]: the candidate pass's winner retest
 };
+static_assert(sizeof(KParams) == 512, "KParams is the kernel argument: no field is added, removed or moved");
 
-// The render kernel launch_render takes and its BVH walk's LDS stack entries
-// (rt_kernels.hip choose_render).
-struct RenderChoice {
-    bool queue;              // render_kernel_q (else the fixed-grid render_kernel / render_kernel_cuda)
-    int qb;                  // render_kernel_q's QB
-    bool opq;                // ... its OPQ instantiation
-    int stack_cap;           // stack entries of the chosen kernel's BVH walk (0 without a BVH)
-};
-RenderChoice choose_render(const KParams& kp, bool task_ok);
-
+struct RenderPlan;                                    // rt_launch_plan.h
 struct UniBlock { double v[U_COUNT]; };
 
-// launchers (rt_kernels.hip)
+// launchers (rt_kernels.hip): one band of a render or a count run, as planned
 int launch_set_uniforms(const UniBlock& u, double* d_uni, void* stream);
-int launch_render(const KParams& kp, void* stream);
-// Name of the render kernel the calling thread's last launch_render chose.
+int launch_render(const KParams& kp, const RenderPlan& plan, void* stream);
+// Name of the render kernel of the calling thread's last launch_render.
 const char* last_render_kernel();
-int launch_count(const KParams& kp, void* stream);
+int launch_count(const KParams& kp, const RenderPlan& plan, void* stream);
 int launch_assemble(const double* gathered, long long rank_stride, int world, int tile_rows,
                     int rows_per_rank, int W, int H, double* out, void* stream);
 int launch_selftest(int op, const double* d_in, double* d_out, int n, void* stream);

@@ -7,7 +7,8 @@
 //
 // Semantics follow main.c (the authoritative CPU path), not main_cuda.cu
 // (reference lines -> function, file; this file includes the headers in
-// definition order and keeps the small kernels, launchers and dispatch):
+// definition order and keeps the small kernels and the launchers, which execute
+// the host's plan, rt_launch_plan.cpp plan_render):
 //   fill_canva        main.c:245-284      -> render_kernel_q (task queue; decode_task is its one
 //                                            task decoder), rt_queue.h / render_kernel (fixed
 //                                            grid; tile_row: local tile row -> frame row),
@@ -65,6 +66,7 @@
 #include "rt/rt.h"
 #include "rt_internal.h"
 #include "rt_bvh.h"
+#include "rt_launch_plan.h"
 #include "rt_device_math.h"
 
 // ---- Build-time tunables (numeric; a tuning run varies these) ----------
@@ -333,60 +335,45 @@ static dim3 grid_for(const KParams& kp)
 
 // Kernel instantiation per scene features: BVH traversal and the sky branch
 // are compiled only into the variants that use them, so a sphere-only scene
-// runs a kernel without their registers.
+// runs a kernel without their registers.  (A wide tree, rt_bvh.h: the
+// instantiations with uint32 stack entries.)
 template <bool COUNT>
-static void launch_variant(const KParams& kp_in, void* stream)
+static void launch_variant(const KParams& kp, const RenderPlan& pl, void* stream)
 {
-    const dim3 g = grid_for(kp_in);
-    const hipStream_t st = (hipStream_t)stream;
-    KParams kp = kp_in;
-    // a wide tree (rt_bvh.h): the instantiations with uint32 stack entries
-    if (kp.bvh && kp.bvh_wide) {
-        if (kp.cuda) hipLaunchKernelGGL((render_kernel_cuda_w<COUNT>), g, dim3(256), 0, st, kp);
-        else if (kp.sky) hipLaunchKernelGGL((render_kernel_w<COUNT, true>), g, dim3(256), 0, st, kp);
-        else hipLaunchKernelGGL((render_kernel_w<COUNT, false>), g, dim3(256), 0, st, kp);
-    } else if (kp.cuda && kp.bvh) hipLaunchKernelGGL((render_kernel_cuda<COUNT, true>), g, dim3(256), 0, st, kp);
-    else if (kp.cuda) hipLaunchKernelGGL((render_kernel_cuda<COUNT, false>), g, dim3(256), 0, st, kp);
-    else if (kp.bvh && kp.sky) hipLaunchKernelGGL((render_kernel<COUNT, true, true>), g, dim3(256), 0, st, kp);
-    else if (kp.bvh) hipLaunchKernelGGL((render_kernel<COUNT, true, false>), g, dim3(256), 0, st, kp);
-    else if (kp.sky) hipLaunchKernelGGL((render_kernel<COUNT, false, true>), g, dim3(256), 0, st, kp);
-    else hipLaunchKernelGGL((render_kernel<COUNT, false, false>), g, dim3(256), 0, st, kp);
+    using K = void (*)(const KParams);
+    const K kernel =
+        pl.wide   ? (pl.cuda ? K(render_kernel_cuda_w<COUNT>) : pl.sky ? K(render_kernel_w<COUNT, true>) : K(render_kernel_w<COUNT, false>))
+        : pl.cuda ? (pl.bvh ? K(render_kernel_cuda<COUNT, true>) : K(render_kernel_cuda<COUNT, false>))
+        : pl.bvh  ? (pl.sky ? K(render_kernel<COUNT, true, true>) : K(render_kernel<COUNT, true, false>))
+                  : (pl.sky ? K(render_kernel<COUNT, false, true>) : K(render_kernel<COUNT, false, false>));
+    hipLaunchKernelGGL(kernel, grid_for(kp), dim3(256), 0, (hipStream_t)stream, kp);
 }
 
 // The 28 render_kernel_q instantiations, (QB, OPQ) x sky x AO, described once:
-// with_queue_variant maps the runtime tuple to a QVariant and hands it to f, so
-// the kernel pointer, its name and its occupancy cache cannot disagree.
+// with_queue_variant maps the plan's tuple to a QVariant and hands it to f, so
+// the kernel pointer and its occupancy cache cannot disagree.
 template <bool SKY, int AOM, int QB, bool OPQ>
 struct QVariant {
     static constexpr void (*kernel)(const KParams) = render_kernel_q<SKY, AOM, QB, OPQ>;
-    static const char* name()          // tests and bench.py read these (last_render_kernel)
-    {
-        return QB == 3    ? (OPQ ? "render_kernel_q<QB=3,OP>" : "render_kernel_q<QB=3>")
-               : QB == 4  ? "render_kernel_q<QB=4>"
-               : QB == 5  ? "render_kernel_q<QB=5>"
-               : QB == -2 ? "render_kernel_q<QB=-2>"
-               : QB == -1 ? "render_kernel_q<QB=-1>"
-                          : "render_kernel_q<QB=0>";
-    }
 };
 template <int QB, bool OPQ, class F>
-static void with_queue_variant_qb(bool sky, bool ao, F&& f)
+static void with_queue_variant_qb(const RenderPlan& pl, F&& f)
 {
-    if (sky && ao) f(QVariant<true, AO_ON, QB, OPQ>{});
-    else if (sky) f(QVariant<true, AO_OFF, QB, OPQ>{});
-    else if (ao) f(QVariant<false, AO_ON, QB, OPQ>{});
+    if (pl.sky && pl.ao) f(QVariant<true, AO_ON, QB, OPQ>{});
+    else if (pl.sky) f(QVariant<true, AO_OFF, QB, OPQ>{});
+    else if (pl.ao) f(QVariant<false, AO_ON, QB, OPQ>{});
     else f(QVariant<false, AO_OFF, QB, OPQ>{});
 }
 template <class F>
-static void with_queue_variant(int qb, bool opq, bool sky, bool ao, F&& f)
+static void with_queue_variant(const RenderPlan& pl, F&& f)
 {
-    if (qb == 3 && opq) with_queue_variant_qb<3, true>(sky, ao, f);
-    else if (qb == 3) with_queue_variant_qb<3, false>(sky, ao, f);
-    else if (qb == 4) with_queue_variant_qb<4, false>(sky, ao, f);
-    else if (qb == 5) with_queue_variant_qb<5, false>(sky, ao, f);
-    else if (qb == -2) with_queue_variant_qb<-2, false>(sky, ao, f);
-    else if (qb < 0) with_queue_variant_qb<-1, false>(sky, ao, f);
-    else with_queue_variant_qb<0, false>(sky, ao, f);
+    if (pl.qb == 3 && pl.opq) with_queue_variant_qb<3, true>(pl, f);
+    else if (pl.qb == 3) with_queue_variant_qb<3, false>(pl, f);
+    else if (pl.qb == 4) with_queue_variant_qb<4, false>(pl, f);
+    else if (pl.qb == 5) with_queue_variant_qb<5, false>(pl, f);
+    else if (pl.qb == -2) with_queue_variant_qb<-2, false>(pl, f);
+    else if (pl.qb == -1) with_queue_variant_qb<-1, false>(pl, f);
+    else with_queue_variant_qb<0, false>(pl, f);
 }
 
 // Resident blocks of the queue kernel on this device (grid of render_kernel_q).
@@ -421,66 +408,17 @@ static unsigned qdiv_magic(unsigned d) { return d ? (unsigned)(0xffffffffull / d
 static thread_local const char* t_last_kernel = "none";
 const char* last_render_kernel() { return t_last_kernel; }
 
-// Which render kernel a launch takes (launch_render) and the LDS stack entries
-// that kernel gives a BVH walk.  task_ok: the launch has render_kernel_q's task
-// counter (spp_chunks > 1 and the band's tasks fit 32 bits, launch_on_stream).
-// Node visits per lane and round: 4 for shallow trees (128-byte nodes, kp.bvh),
-// 3 for deep ones (kp.bvh_steps, host; compile-time per instantiation).  The
-// deep-tree instantiation walks the 64-byte nodes kp.bvhh: a deep tree that
-// pack_bvh_h refused (a coordinate beyond binary16's range, a leaf index above
-// 65535, an oversized leaf) renders with QB 4's walk when its stack fits there,
-// else with the fixed-grid kernel; a shallow one keeps the queue kernel.
-// A wide tree (kp.bvh_wide, rt_bvh.h: indices beyond 16 bits) takes QB 5 --
-// the deep-tree walk over its own 64-byte nodes kp.bvhw with a 24-bit stack --
-// when those nodes packed and its stack bound is at most kStackQW, else the
-// fixed grid's wide instantiation (uint32 stack, kStack4 entries); no narrow
-// kernel ever walks it, and a narrow tree never takes a wide kernel.
-RenderChoice choose_render(const KParams& kp, bool task_ok)
+// One band of a render, as plan_render (rt_launch_plan.cpp) decided it.
+int launch_render(const KParams& kp, const RenderPlan& pl, void* stream)
 {
-    RenderChoice c;
-    c.queue = false;
-    c.qb = 0;
-    c.opq = false;
-    c.stack_cap = kp.bvh ? kStack4 : 0;
-    if (kp.bvh != nullptr && kp.bvh_wide) {
-        if (task_ok && kp.chunks > 1 && !kp.cuda && !kp.sums && kp.bvhw != nullptr && kp.bvh_stack <= kStackQW) {
-            c.queue = true;
-            c.qb = 5;
-            c.stack_cap = kStackQW;
-        }
-        return c;
-    }
-    bool qbvh = false;
-    if (kp.bvh != nullptr && kp.bvh_stack <= kStackQN) {
-        c.qb = kp.bvh_steps <= 3 || kp.bvh_stack > kStackQ4 ? 3 : 4;
-        // a deep tree without 64-byte nodes whose stack fits QB 4's walks the
-        // 128-byte nodes there (e.g. main()'s pyramide_eau mesh: triangles of
-        // ~4000 units pad their boxes beyond binary16's range)
-        if (c.qb == 3 && kp.bvhh == nullptr && kp.bvh_stack <= kStackQ4 && !kp.bvh_far) c.qb = 4;
-        if (c.qb == 4 && kp.bvh_far) c.qb = 3;           // QB 4 has no far-origin margins (ray32<false>)
-        qbvh = c.qb == 4 || kp.bvhh != nullptr;
-    }
-    if (task_ok && kp.chunks > 1 && (!kp.bvh || qbvh) && !kp.cuda && !kp.sums) {
-        c.queue = true;
-        if (!qbvh) c.qb = kp.nt == 0 ? (kp.opaque ? -2 : -1) : 0;
-        c.opq = c.qb == 3 && kp.opaque_all && kp.bvh_stack <= kStackQ && !kp.bvh_far;
-        if (kp.bvh) c.stack_cap = c.qb == 4 ? kStackQ4 : c.opq ? kStackQ : kStackQN;
-    }
-    return c;
-}
-
-int launch_render(const KParams& kp, void* stream)
-{
-    const RenderChoice rc = choose_render(kp, kp.task_ctr != nullptr);
-    if (rc.queue) {
+    t_last_kernel = pl.name;
+    if (pl.queue) {
         const hipStream_t st = (hipStream_t)stream;
-        const bool sky = kp.sky != nullptr, ao = kp.useAO != 0;
         (void)hipMemsetAsync(kp.task_ctr, 0, sizeof(unsigned), st);
         void (*kernel)(const KParams) = nullptr;
         unsigned nb = 0;
-        with_queue_variant(rc.qb, rc.opq, sky, ao, [&](auto v) {
+        with_queue_variant(pl, [&](auto v) {
             kernel = v.kernel;
-            t_last_kernel = v.name();
             nb = queue_grid(v);
         });
         unsigned long long* tr = nullptr;
@@ -508,10 +446,7 @@ int launch_render(const KParams& kp, void* stream)
             }
         }
     } else {
-        launch_variant<false>(kp, stream);
-        t_last_kernel = kp.cuda ? "render_kernel_cuda"
-                        : kp.bvh ? (kp.bvh_wide ? "render_kernel<BVH32>" : "render_kernel<BVH>")
-                                 : "render_kernel";
+        launch_variant<false>(kp, pl, stream);
     }
     if (kp.chunks > 1) {
         const long long npx = (long long)kp.band_rows * kp.W;
@@ -520,9 +455,9 @@ int launch_render(const KParams& kp, void* stream)
     return (int)hipGetLastError();
 }
 
-int launch_count(const KParams& kp, void* stream)
+int launch_count(const KParams& kp, const RenderPlan& pl, void* stream)
 {
-    launch_variant<true>(kp, stream);
+    launch_variant<true>(kp, pl, stream);
     return (int)hipGetLastError();
 }
 

@@ -14,7 +14,7 @@
 namespace rt {
 
 // The scalars of one prepared scene (rt_device_scene carries them as they are;
-// make_kparams turns them into KParams fields and launch gates).
+// fill_kparams, rt_launch_plan.h, turns them into KParams fields and launch gates).
 struct SceneFacts {
     int ns = 0, ns_pad = 0, nt = 0, tw = 1, th = 1;
     long long n_texels = 0;

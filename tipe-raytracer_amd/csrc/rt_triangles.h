@@ -122,14 +122,9 @@ __device__ __forceinline__ unsigned short* bvh_stack()
 // deep-tree instantiations (QB = 3) get kStackQ = 24 entries (12 KiB) when every
 // material is opaque (OPQ: incomingLight also lives in LDS) and kStackQN = 32
 // (16 KiB) otherwise, which keeps both at <= 40 KiB, i.e. 4 blocks (16 waves) per
-// CU.  The QB = 4 instantiation (shallow trees: bvh_steps 4, i.e. depth4 <= 4) is
-// admitted only when the tree's exact stack bound (rt_bvh.cpp stack4) is at most
-// kStackQ4 = 14 entries, so its top-node cache and the task table fit the same
-// 40 KiB.  An opaque tree whose bound lies in (24, 32] takes the non-OPQ QB = 3
-// kernel; a bound above 32 the fixed grid (kStack4).  choose_render (rt_kernels.hip) is the
-// one place that decides; the host stores its stack in KParams::stack_cap, which
-// the COUNT runs check every push against (RT_CNT_BVH_STACK_OVER).
-constexpr int kStackQ = 24, kStackQN = 32, kStackQ4 = 14;
+// CU.  The QB = 4 instantiation has kStackQ4 = 14 entries, so its top-node cache
+// and the task table fit the same 40 KiB.  (The capacities are in rt_bvh.h; who
+// is admitted where is plan_render's rule, rt_launch_plan.cpp.)
 template <int QB, bool OPQ>
 __device__ __forceinline__ unsigned short* bvh_stack_q()
 {
@@ -159,7 +154,6 @@ __device__ __forceinline__ SE* bvh_stack_of()
 // uint16 column and a uint8 column, 24 KiB: with the 22 KiB of sums and draws
 // 46 KiB per block, three blocks (12 waves) per CU.  (32 uint32 entries would
 // make it 54 KiB: two blocks.)
-constexpr int kStackQW = 32;
 struct Stack24 {
     unsigned short* lo;
     unsigned char* hi;
@@ -235,7 +229,7 @@ __device__ __forceinline__ void ray32_axis(double oc, double dc, float rbox, flo
     b = -oi + E;
 }
 // FAR: compiled into the kernels that may meet such origins (the non-opaque
-// deep-tree queue kernel and the fixed-grid ones); launch_render gives the
+// deep-tree queue kernel and the fixed-grid ones); plan_render gives the
 // others (C4's OPQ kernel, QB 4) only launches with kp.bvh_far 0.
 template <bool FAR = true>
 __device__ __forceinline__ Ray32 ray32(const KParams& kp, const V3 o, const V3 d)
