@@ -51,7 +51,7 @@ class Case:
 
 
 def _random(seed, bounce_hi=9):
-    """tests/test_gpu_fuzz.random_scene(seed) inside a black, opaque sphere of
+    """tests/helpers.random_scene(seed) inside a black, opaque sphere of
     radius 1e4 (appended last).  Without it a primary miss leaves the
     reference's albedo/normal undefined: closest_hit (main.c:54-56) never sets
     HitInfo.mat / .normal on a miss and tracer (main.c:137-140) reads them, so
@@ -59,18 +59,15 @@ def _random(seed, bounce_hi=9):
     build defines 0.  Secondary misses (main.c:236-238) stay
     covered by the README-box cases (the box is open towards +z)."""
     def build():
-        from test_gpu_fuzz import random_scene     # noqa: WPS433 (shared generator)
-        from tipe_rt.types import Sphere, Vec3
-        bundle, p = random_scene(seed, bounce_hi=bounce_hi)
-        n = len(bundle.spheres)
-        sph = (Sphere * (n + 1))()
-        for k in range(n):
-            sph[k] = bundle.spheres[k]
-        sph[n].center = Vec3(0.0, 0.0, 0.0)
-        sph[n].radius = 1e4
-        sph[n].mat = scenes.material((0, 0, 0), (0, 0, 0), 0.0, 0.0, 1.0, 1.0)
+        bundle, p = helpers.random_scene(seed, bounce_hi=bounce_hi)
+        black = scenes.material((0, 0, 0), (0, 0, 0), 0.0, 0.0, 1.0, 1.0)
+        sph = helpers.spheres_plus(bundle.spheres, [((0.0, 0.0, 0.0), 1e4, black)])
         return helpers.SceneBundle(sph, bundle.mesh), p
     return build
+
+
+# The `what` texts below are recorded in the fixtures under tests/golden/, so
+# they keep naming random_scene by its first home, tests/test_gpu_fuzz.
 
 
 def _glass():

@@ -16,6 +16,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import mesh_rows
 from tipe_rt import scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,11 +39,6 @@ def run(checker, tris):
     rec = json.loads(p.stdout.strip().splitlines()[-1])
     assert p.returncode == 0, rec
     return rec
-
-
-def mesh_rows(tris):
-    return np.array([[t.A.e[0], t.A.e[1], t.A.e[2], t.B.e[0], t.B.e[1], t.B.e[2], t.C.e[0], t.C.e[1], t.C.e[2]]
-                     for t in tris])
 
 
 def test_c4_tree_nodes_contain_their_boxes(checker):

@@ -17,9 +17,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import mesh_rows
 from tipe_rt import scenes
-
-from test_bvh_pack import mesh_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 K_STACK_Q = 24          # rt_bvh.h kStackQ

@@ -125,20 +125,20 @@ def test_cuda_mesh_box_culls_flat_axis_aligned_mesh():
 # ---- GPU: kernel vs restatement ---------------------------------------------
 @pytest.mark.gpu
 def test_gpu_cuda_mode_cornell_bitexact():
-    from test_gpu_parity import check_parity
+    from gpu_driver import check_parity
     check_parity(helpers.cornell(), helpers.params(40, 30, 8, 5, semantics=RT_SEM_CUDA))
 
 
 @pytest.mark.gpu
 def test_gpu_cuda_mode_ao_and_chunks_bitexact():
-    from test_gpu_parity import check_parity
+    from gpu_driver import check_parity
     check_parity(helpers.cornell(), helpers.params(32, 24, 8, 6, use_ao=True, ao=2.5, chunks=4,
                                                    semantics=RT_SEM_CUDA))
 
 
 @pytest.mark.gpu
 def test_gpu_cuda_mode_pyramid_mesh_bitexact():
-    from test_gpu_parity import check_parity
+    from gpu_driver import check_parity
     mesh = scenes.with_cuda_materials(scenes.pyramid_mesh())
     check_parity(helpers.SceneBundle(scenes.cornell_spheres(), mesh), helpers.params(40, 30, 8, 6,
                                                                                      semantics=RT_SEM_CUDA))
@@ -146,7 +146,7 @@ def test_gpu_cuda_mode_pyramid_mesh_bitexact():
 
 @pytest.mark.gpu
 def test_gpu_cuda_mode_tree_bvh_bitexact():
-    from test_gpu_parity import check_parity
+    from gpu_driver import check_parity
     mesh = scenes.with_cuda_materials(scenes.tree_mesh())
     bundle = helpers.SceneBundle(scenes.cornell_spheres(), mesh)
     check_parity(bundle, helpers.params(24, 18, 4, 6, use_ao=True, ao=3.0, semantics=RT_SEM_CUDA))
@@ -154,17 +154,12 @@ def test_gpu_cuda_mode_tree_bvh_bitexact():
 
 @pytest.mark.gpu
 def test_gpu_cuda_mode_counters_match_oracle():
-    import torch
+    from gpu_driver import gpu_counts
     mesh = scenes.with_cuda_materials(scenes.pyramid_mesh())
     bundle = helpers.SceneBundle(scenes.cornell_spheres(), mesh)
     p = helpers.params(24, 18, 4, 6, use_ao=True, ao=2.5, semantics=RT_SEM_CUDA)
     ref = helpers.oracle_render(bundle, p, counters=True)["counters"]
-    ds = tipe_rt.DeviceScene(bundle.scene, 0)
-    d_cnt = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device="cuda:0")
-    tipe_rt.count_async(ds, p, tipe_rt.band_tiling(0, 17), d_cnt.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    ds.close()
-    got = d_cnt.cpu().numpy().astype(np.uint64)
+    got = gpu_counts(bundle, p)
     # texture hits are a main.c event (tri_uvmapping); CUDA mode has none
     for k in (tipe_rt.types.RT_CNT_SAMPLES, tipe_rt.types.RT_CNT_CASTS, tipe_rt.types.RT_CNT_SPHERE_TESTS,
               tipe_rt.types.RT_CNT_SPHERE_DISC, tipe_rt.types.RT_CNT_SHADE, tipe_rt.types.RT_CNT_RNG_DRAWS):

@@ -2,8 +2,8 @@
 wavelet filter of the library's own -- not OIDN -- behind the denoise hook.
 
 rt.h specifies the filter operation by operation in IEEE binary32, so the
-NumPy float32 restatement below (written from that text, not from the kernel)
-must equal the GPU bit for bit.  Parameter defaults, the workspace size and
+NumPy float32 restatement in tests/denoise_support.py (written from that text,
+not from the kernel) must equal the GPU bit for bit.  Parameter defaults, the workspace size and
 argument validation run without a GPU; everything that filters is gpu-marked."""
 import ctypes as C
 import math
@@ -14,55 +14,7 @@ import pytest
 import helpers
 import tipe_rt
 from tipe_rt import types as T
-from test_denoise_hook import frames
-
-F = np.float32
-TAP_H = np.array([1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0], dtype=F)
-DEFAULTS = dict(iterations=4, sigma_color=1.0, sigma_normal=0.5, sigma_albedo=0.25)
-
-
-def restate(canva, albedo, normal, iterations=4, sigma_color=1.0, sigma_normal=0.5, sigma_albedo=0.25):
-    """rt.h's filter in float32: returns (c before quantisation, canva after)."""
-    c = canva.astype(F) / F(255.0)
-    a = None if albedo is None else albedo.astype(F)
-    n = None if normal is None else normal.astype(F)
-    H, W = c.shape[:2]
-    one = F(1.0)
-    sn2 = F(sigma_normal) * F(sigma_normal)
-    sa2 = F(sigma_albedo) * F(sigma_albedo)
-
-    def d2(X, Q, P):
-        D = X[Q] - X[P]
-        return (D[..., 0] * D[..., 0] + D[..., 1] * D[..., 1]) + D[..., 2] * D[..., 2]
-
-    def k(x):
-        return one / (one + x)
-
-    for i in range(iterations):
-        s = 1 << i
-        sc = F(sigma_color) * F(2.0 ** -i)
-        sc2 = sc * sc
-        acc = np.zeros((H, W, 3), dtype=F)
-        ws = np.zeros((H, W), dtype=F)
-        for dy in range(-2, 3):
-            for dx in range(-2, 3):
-                oy, ox = s * dy, s * dx
-                y0, y1, x0, x1 = max(0, -oy), min(H, H - oy), max(0, -ox), min(W, W - ox)
-                if y0 >= y1 or x0 >= x1:
-                    continue                      # the tap is outside the image for every pixel
-                P = (slice(y0, y1), slice(x0, x1))
-                Q = (slice(y0 + oy, y1 + oy), slice(x0 + ox, x1 + ox))
-                w = (TAP_H[dy + 2] * TAP_H[dx + 2]) * k(d2(c, Q, P) / sc2)
-                if n is not None:
-                    w = w * k(d2(n, Q, P) / sn2)
-                if a is not None:
-                    w = w * k(d2(a, Q, P) / sa2)
-                assert w.dtype == F
-                acc[P] = acc[P] + w[..., None] * c[Q]
-                ws[P] = ws[P] + w
-        c = acc / ws[..., None]
-        assert c.dtype == F
-    return c, np.trunc(c * F(255.0)).astype(np.int64).astype(np.float64)
+from denoise_support import F, TAP_H, DEFAULTS, restate, params_of, device_denoise, frames
 
 
 def restate_scalar(canva, albedo, normal, iterations=4, sigma_color=1.0, sigma_normal=0.5, sigma_albedo=0.25):
@@ -146,26 +98,6 @@ def evaluate_f64(canva, albedo, normal, iterations=4, sigma_color=1.0, sigma_nor
                 ws += w
         c = acc / ws[..., None]
     return c
-
-
-def params_of(**kw):
-    return tipe_rt.denoise_params(**kw)
-
-
-def device_denoise(canva, albedo, normal, **kw):
-    """rt_denoise_async on device copies: (color3_out, canva, albedo, normal) back on the host."""
-    import torch
-    dev = torch.device("cuda:0")
-    H, W = canva.shape[:2]
-    t = [None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (canva, albedo, normal)]
-    nbytes = tipe_rt.lib().rt_denoise_workspace_bytes(W, H)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    c3 = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
-    tipe_rt.denoise_async(W, H, t[0].data_ptr(), None if t[1] is None else t[1].data_ptr(),
-                          None if t[2] is None else t[2].data_ptr(), params_of(**kw), ws.data_ptr(), nbytes,
-                          c3.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return [c3.cpu().numpy()] + [None if x is None else x.cpu().numpy() for x in t]
 
 
 def check_bit_exact(W, H, seed, use_albedo=True, use_normal=True, **kw):
@@ -370,7 +302,7 @@ def test_denoised_frame_is_closer_to_the_converged_one(scene):
     """64x48, 6 bounces, chunks = 1: a 16-spp frame (seed 7), denoised with
     the default parameters, against the 2048-spp frame (seed 1010):
     RMSE(denoised, ref) <= 0.6 RMSE(noisy, ref) over the canva.  CPU oracle
-    renders filtered with the restatement above give ratios of 0.481
+    renders filtered with the restatement give ratios of 0.481
     (cornell) and 0.494 (pyramid); render and filter are both bit-exact, so the
     GPU reproduces them."""
     bundle = helpers.cornell() if scene == "cornell" else helpers.pyramid_scene()

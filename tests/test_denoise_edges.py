@@ -4,8 +4,8 @@ tile, the second trip of the grid-stride kernels, exact ties and truncation
 edges, binary32 subnormals, and the rt_denoise_async / rt_denoise_host
 contract of rt.h (caller's stream, private workspace, threads).
 
-Every GPU comparison is bit for bit against the restatement of
-test_denoise_atrous.py, which its own CPU tests guard.
+Every GPU comparison is bit for bit against the restatement in
+denoise_support.py, which test_denoise_atrous.py's CPU tests guard.
 
 Which pass kernel a case runs (launch_pass: tiled for steps 1..16, plain for
 32..128, <ALB, NRM> from the planes given):
@@ -30,10 +30,9 @@ import pytest
 
 import helpers
 import tipe_rt
-from test_denoise_atrous import restate, DEFAULTS, params_of
-from test_denoise_hook import frames, reference_pack
+from gpu_driver import device_planes
+from denoise_support import F, DEFAULTS, restate, params_of, frames, reference_pack
 
-F = np.float32
 BIG = (1024, 683)          # 2 098 176 floats: just above the 8192 x 256 threads of the grid-stride kernels
 
 
@@ -285,7 +284,7 @@ def test_render_then_denoise_stays_on_the_device():
     ds = tipe_rt.DeviceScene(bundle.scene, 0)
     st = torch.cuda.Stream()
     with torch.cuda.stream(st):
-        planes = [torch.full((H, W, 3), -1.0, dtype=torch.float64, device="cuda:0") for _ in range(3)]
+        planes = device_planes(H, W, n=3)
         ws = torch.empty(ws_bytes(W, H), dtype=torch.uint8, device="cuda:0")
     tipe_rt.render_async(ds, p, tipe_rt.band_tiling(0, H - 1), *[t.data_ptr() for t in planes], stream=st.cuda_stream)
     tipe_rt.denoise_async(W, H, *[t.data_ptr() for t in planes], params_of(), ws.data_ptr(), ws.numel(), None,

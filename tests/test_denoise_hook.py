@@ -10,24 +10,12 @@ import pytest
 
 import helpers
 import tipe_rt
-
-
-def reference_pack(canva, albedo, normal):
-    """denoiser.h:44-60: (float)canva / 255.0f, (float)albedo, (float)normal."""
-    return (canva.astype(np.float32) / np.float32(255.0), albedo.astype(np.float32), normal.astype(np.float32))
+from denoise_support import frames, reference_pack
 
 
 def reference_unpack(color3):
     """denoiser.h:80-84: canva = (int)(f * 255.0f), stored in a double."""
     return np.trunc(color3.astype(np.float32) * np.float32(255.0)).astype(np.int64).astype(np.float64)
-
-
-def frames(H=7, W=9, seed=0):
-    rng = np.random.default_rng(seed)
-    canva = rng.integers(0, 256, (H, W, 3)).astype(np.float64)
-    albedo = rng.uniform(0, 1, (H, W, 3))
-    normal = rng.uniform(-1, 1, (H, W, 3))
-    return canva, albedo, normal
 
 
 def test_pack_matches_denoiser_h():

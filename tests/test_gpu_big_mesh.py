@@ -12,86 +12,43 @@ radiance, against the oracle (which scans every triangle) or against the
 GPU's own every-triangle scan (accel = RT_ACCEL_NONE), and every case asserts
 the kernel the launch took.  Each scene is uploaded once.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import helpers
 import tipe_rt
+from gpu_driver import Uploaded, assert_same_frame
+from kernel_cases import QB5, BVH32
 from tipe_rt import scenes
-from tipe_rt.types import (Sphere, Triangle, RT_ACCEL_NONE, RT_CNT_BVH_NODES, RT_CNT_BVH_STACK_OVER,
-                           RT_CNT_BVH_TRI_TESTS, RT_CNT_TRI_TESTS)
-
-from test_gpu_parity import assert_same
+from tipe_rt.types import (Sphere, RT_ACCEL_NONE, RT_CNT_BVH_NODES, RT_CNT_BVH_STACK_OVER, RT_CNT_BVH_TRI_TESTS,
+                           RT_CNT_TRI_TESTS)
 
 pytestmark = pytest.mark.gpu
 
-QB5, BVH32 = "render_kernel_q<QB=5>", "render_kernel<BVH32>"
 
-
-class Uploaded:
-    """A SceneBundle and its rt_scene_upload handle."""
-
-    def __init__(self, spheres, mesh):
-        self.bundle = helpers.SceneBundle(spheres, mesh)
-        self.ds = tipe_rt.DeviceScene(self.bundle.scene, 0)
-
-    def render(self, p):
-        """(canva, albedo, normal, radiance) and the kernel's name."""
-        import torch
-        W, H = p.largeur_image, p.hauteur_image
-        bufs = [torch.full((H, W, 3), -1.0, dtype=torch.float64, device="cuda:0") for _ in range(4)]
-        tipe_rt.render_async(self.ds, p, tipe_rt.band_tiling(0, H - 1), *(b.data_ptr() for b in bufs),
-                             torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        return [b.cpu().numpy() for b in bufs], tipe_rt.last_render_kernel()
-
-    def counts(self, p):
-        import torch
-        d = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device="cuda:0")
-        tipe_rt.count_async(self.ds, p, tipe_rt.band_tiling(0, p.hauteur_image - 1), d.data_ptr(),
-                            torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        return [int(x) for x in d.cpu()]
-
-
-def same_frames(got, ref):
-    for g, r, what in zip(got, ref, ("canva", "albedo", "normal", "radiance")):
-        assert_same(g, r, what)
+def uploaded(spheres, mesh):
+    return Uploaded(helpers.SceneBundle(spheres, mesh))
 
 
 def against_oracle(up, p, nthreads=8):
-    ref = helpers.oracle_render(up.bundle, p, nthreads=nthreads)
-    got, kernel = up.render(p)
-    same_frames(got, [ref["canva"], ref["albedo"], ref["normal"], ref["radiance"]])
-    return kernel
+    assert_same_frame(up.render(p), helpers.oracle_render(up.bundle, p, nthreads=nthreads))
+    return up.kernel
 
 
 def against_brute_force(up, W, H, spp, bounces, **kw):
     """The BVH render against the same launch with accel = RT_ACCEL_NONE."""
-    ref, kref = up.render(helpers.params(W, H, spp, bounces, accel=RT_ACCEL_NONE, **kw))
-    assert "BVH" not in kref and "QB=5" not in kref, kref
-    got, kernel = up.render(helpers.params(W, H, spp, bounces, **kw))
-    same_frames(got, ref)
-    return kernel
-
-
-def truncated(mesh, nt):
-    tris, qm, mats, tw, th, nm = mesh
-    t2 = (Triangle * nt)()
-    q2 = (C.c_int * nt)()
-    C.memmove(t2, tris, C.sizeof(Triangle) * nt)
-    C.memmove(q2, qm, C.sizeof(C.c_int) * nt)
-    return t2, q2, mats, tw, th, nm
+    ref = up.render(helpers.params(W, H, spp, bounces, accel=RT_ACCEL_NONE, **kw))
+    assert "BVH" not in up.kernel and "QB=5" not in up.kernel, up.kernel
+    assert_same_frame(up.render(helpers.params(W, H, spp, bounces, **kw)), ref)
+    return up.kernel
 
 
 @pytest.fixture(scope="module")
 def big():
     """180 000 triangles: node indices pass 16 bits too (90 671 nodes)."""
-    up = Uploaded(scenes.cornell_spheres(), scenes.heightfield_mesh(300, 1, 0.25, scenes.README_FLOOR))
+    up = uploaded(scenes.cornell_spheres(), scenes.heightfield_mesh(300, 1, 0.25, scenes.README_FLOOR))
     yield up
-    up.ds.close()
+    up.close()
 
 
 @pytest.fixture(scope="module")
@@ -102,9 +59,9 @@ def alpha_mesh():
 
 @pytest.fixture(scope="module")
 def mid(alpha_mesh):
-    up = Uploaded(scenes.cornell_spheres(), alpha_mesh)
+    up = uploaded(scenes.cornell_spheres(), alpha_mesh)
     yield up
-    up.ds.close()
+    up.close()
 
 
 def test_180000_triangles_match_the_oracle(big):
@@ -128,10 +85,10 @@ def test_alpha_holes_and_refraction_through_the_wide_kernel(mid):
 def test_far_origins_under_the_sky_sphere(alpha_mesh):
     """main.c:346's radius-1e5 sky, zero-throughput exit off: sky hits go on
     from |o| ~ 1e5 through the wide tree with per-ray margins (ray32<true>)."""
-    up = Uploaded(scenes.main_spheres(), alpha_mesh)
+    up = uploaded(scenes.main_spheres(), alpha_mesh)
     with tipe_rt.reference_counts():
         assert against_brute_force(up, 32, 24, 2, 4, chunks=4) == QB5
-    up.ds.close()
+    up.close()
 
 
 def test_counters_show_the_tree_culls(big):
@@ -146,24 +103,24 @@ def test_boundary_between_narrow_and_wide(alpha_mesh, nt, kernel):
     """65 535 triangles keep the narrow fixed-grid kernel they took before wide
     trees existed (above 32768 triangles no narrow tree takes the queue
     kernel); one more triangle makes the tree wide."""
-    up = Uploaded(scenes.cornell_spheres(), truncated(alpha_mesh, nt))
+    up = uploaded(scenes.cornell_spheres(), helpers.mesh_of(alpha_mesh, nt))
     assert against_brute_force(up, 32, 24, 1, 4) == kernel
-    up.ds.close()
+    up.close()
 
 
 def test_leaves_of_three(alpha_mesh, monkeypatch):
     monkeypatch.setenv("RT_BVH_LEAF", "3")               # read by rt_scene_upload's build
-    up = Uploaded(scenes.cornell_spheres(), alpha_mesh)
+    up = uploaded(scenes.cornell_spheres(), alpha_mesh)
     monkeypatch.delenv("RT_BVH_LEAF")
     assert against_brute_force(up, 32, 24, 2, 4, chunks=4) == QB5
-    up.ds.close()
+    up.close()
 
 
 def test_scene_beyond_binary16_takes_the_wide_fixed_grid(alpha_mesh):
     """Every coordinate x 1e5: the BvhNodeW form does not pack, so even a
     launch with a task queue walks the 128-byte nodes on the fixed grid."""
     k = 1e5
-    tris, qm, mats, tw, th, nm = truncated(alpha_mesh, len(alpha_mesh[0]))
+    tris, qm, mats, tw, th, nm = helpers.mesh_of(alpha_mesh, len(alpha_mesh[0]))
     np.frombuffer(tris, dtype=np.float64).reshape(len(tris), -1)[:, :9] *= k
     sun = (Sphere * 1)(scenes.main_spheres()[0])
     sun[0].center = scenes.Vec3(0.5 * k, 2.8 * k, -1.2 * k)
@@ -171,6 +128,6 @@ def test_scene_beyond_binary16_takes_the_wide_fixed_grid(alpha_mesh):
     cam = scenes.README_CAMERA
     camera = helpers.camera_of(dict(cam, origin=tuple(k * x for x in cam["origin"]),
                                     target=tuple(k * x for x in cam["target"])))
-    up = Uploaded(sun, (tris, qm, mats, tw, th, nm))
+    up = uploaded(sun, (tris, qm, mats, tw, th, nm))
     assert against_brute_force(up, 32, 24, 2, 4, chunks=4, cam=camera, focus=3.0 * k) == BVH32
-    up.ds.close()
+    up.close()

@@ -15,11 +15,9 @@ import pytest
 
 import helpers
 import tipe_rt
+from gpu_driver import assert_stack_bound_holds, render_and_compare
 from tipe_rt import scenes
-from tipe_rt.types import Sphere, Vec3
-
-from test_gpu_bvh_fallback import render_and_compare
-from test_gpu_parity import assert_stack_bound_holds
+from tipe_rt.types import Sphere
 
 pytestmark = pytest.mark.gpu
 
@@ -27,14 +25,8 @@ pytestmark = pytest.mark.gpu
 def with_sky(spheres, radius=1e5, diffuse=(0.0, 0.0, 0.0)):
     """The spheres plus main.c:346's sky sphere (emission SKY, strength 1),
     last; a non-black diffuse keeps paths alive after a sky hit."""
-    n = len(spheres)
-    arr = (Sphere * (n + 1))()
-    for k in range(n):
-        arr[k] = spheres[k]
-    arr[n].center = Vec3(0.0, 0.0, 0.0)
-    arr[n].radius = radius
-    arr[n].mat = scenes.material(diffuse, scenes.SKY, 1.0, 0.0, 1.0, 1.0)
-    return arr
+    sky = scenes.material(diffuse, scenes.SKY, 1.0, 0.0, 1.0, 1.0)
+    return helpers.spheres_plus(spheres, [((0.0, 0.0, 0.0), radius, sky)])
 
 
 def test_camera_outside_the_tree_bound_walks_the_bvh():

@@ -32,8 +32,8 @@ if __name__ == "__main__":
 
 import helpers
 import tipe_rt
+from gpu_driver import assert_same_frame, gpu_render
 from tipe_rt import scenes
-from tipe_rt.types import Sphere, Vec3
 
 pytestmark = pytest.mark.gpu
 
@@ -43,15 +43,6 @@ SCENES = ["readme", "outside_near", "outside_far", "below_floor", "overlap500", 
 PLANES = ("canva", "albedo", "normal")
 W, H, SPP, BOUNCES = 48, 36, 8, 6
 LMAX = 1004.0                                    # the README box's max |C| + R (its back wall)
-
-
-def bundle_of(rows):
-    arr = (Sphere * len(rows))()
-    for k, (c, r, m) in enumerate(rows):
-        arr[k].center = Vec3(*[float(x) for x in c])
-        arr[k].radius = r
-        arr[k].mat = m
-    return helpers.SceneBundle(arr)
 
 
 def readme_rows():
@@ -80,7 +71,7 @@ def scene_of(name):
                 ((-0.5, 0.2, -2.0), 0.5, M((0, 0, 0), (1.0, 0.6, 0.2), 4.0))]
     else:
         raise KeyError(name)
-    return bundle_of(rows), cam
+    return helpers.SceneBundle(helpers.sphere_array(rows)), cam
 
 
 def params_of(cam):
@@ -150,7 +141,6 @@ def verify_sets(spheres):
 
 def child(mode, path):
     """One mode: every scene's planes and the verify counts of every case set, into path (npz)."""
-    from test_gpu_parity import gpu_render
     if mode != "auto":
         os.environ["RT_CAND_MERGE"] = mode
     else:
@@ -190,16 +180,15 @@ def oracle_planes():
     return ref
 
 
-def same_bytes(a, b):
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
+def planes_of(npz, name):
+    return [npz["%s/%s" % (name, plane)] for plane in PLANES]
 
 
 @pytest.mark.parametrize("name", SCENES)
 def test_modes_give_the_same_bytes(name, by_mode):
-    for plane in PLANES:
-        key = "%s/%s" % (name, plane)
-        for mode in MODES[1:]:
-            assert same_bytes(by_mode[mode][key], by_mode["auto"][key]), (key, mode)
+    for mode in MODES[1:]:
+        assert_same_frame(planes_of(by_mode[mode], name), planes_of(by_mode["auto"], name),
+                          "%s, %s vs auto:" % (name, mode), PLANES, same_bytes=True)
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -208,8 +197,7 @@ def test_bytes_are_the_oracles(name, by_mode, oracle_planes):
     if name == "readme":
         assert ref["canva"].max() > 0
     for mode in MODES:
-        for plane in PLANES:
-            assert same_bytes(by_mode[mode]["%s/%s" % (name, plane)], ref[plane]), (name, plane, mode)
+        assert_same_frame(planes_of(by_mode[mode], name), ref, "%s, %s:" % (name, mode), PLANES, same_bytes=True)
 
 
 @pytest.mark.parametrize("case", ["surface", "near_surface", "bisecting", "scaled"])

@@ -7,115 +7,14 @@ the reference's hard-coded material overrides (texture.h:71-87, indices
 1/3/4), random camera, aperture, focus, AO on/off, spp_chunks, and more
 than 32 triangles on odd seeds so the BVH path runs.  Sizes stay small
 so the oracle finishes in about a second per scene."""
-import ctypes as C
-
-import numpy as np
 import pytest
 
-import helpers
 import tipe_rt
+from gpu_driver import check_parity, assert_stack_bound_holds
+from helpers import random_scene
 from tipe_rt import scenes
-from tipe_rt.types import Sphere, Triangle, Material, Vec3, UV
-from test_gpu_parity import check_parity, assert_stack_bound_holds
 
 pytestmark = pytest.mark.gpu
-
-
-def _zero_some(rng, c, zeros):
-    """With zeros, each colour channel is exactly 0 with probability 0.35,
-    so rayColor reaches (0, 0, 0) and the zero-throughput exit runs."""
-    if not zeros:
-        return c
-    return tuple(0.0 if rng.random() < 0.35 else float(x) for x in c)
-
-
-def random_scene(seed, zeros=False, chunks=None, nt_range=None, spp=None, opaque=False, mesh_p=0.7,
-                 bounce_hi=25, far=False):
-    """bounce_hi: nbRebondMax is drawn from [0, bounce_hi), covering main.c's
-    own default of 20 (main.c:310); the scenes pinned by reference fixtures
-    (tests/composition_cases._random) keep the r05 draw, bounce_hi 9.
-    far: the scene moved into main()'s coordinate regime (below).
-    opaque: only opaque materials (no glass or hole spheres, texels at
-    alpha 1, no material index 3 or 4), the scenes the queue kernel's
-    opaque instantiations take (QB -2, the deep-tree OPQ kernel);
-    mesh_p: probability of a mesh when nt_range is None."""
-    rng = np.random.default_rng(seed)
-    ns = int(rng.integers(1, 14))
-    sph = (Sphere * ns)()
-    for k in range(ns):
-        kind = rng.choice(["diffuse", "mirror", "light", "big"] if opaque
-                          else ["diffuse", "mirror", "glass", "hole", "light", "big"])
-        c = rng.uniform([-2, -2, -6], [2, 2, -1])
-        r = rng.uniform(0.2, 1.2)
-        diff = _zero_some(rng, tuple(rng.uniform(0, 1, 3)), zeros)
-        em, es, refl, alpha, ior = (0, 0, 0), 0.0, 0.0, 1.0, 1.0
-        if kind == "mirror":
-            refl = float(rng.uniform(0.5, 1.0))
-        elif kind == "glass":
-            alpha, ior = float(rng.uniform(0.05, 0.99)), float(rng.uniform(1.0, 2.0))
-        elif kind == "hole":
-            alpha = 0.0
-        elif kind == "light":
-            em, es = tuple(rng.uniform(0.2, 1, 3)), float(rng.uniform(0.5, 5))
-        elif kind == "big":                               # encloses the camera
-            c, r = rng.uniform(-0.5, 0.5, 3), float(rng.uniform(20, 600))
-        sph[k].center = Vec3(*c)
-        sph[k].radius = r
-        sph[k].mat = scenes.material(diff, em, es, refl, alpha, ior)
-    mesh = None
-    if nt_range is not None or rng.random() < mesh_p:
-        nt = int(rng.integers(40, 120)) if seed % 2 else int(rng.integers(1, 20))
-        if nt_range is not None:
-            nt = int(rng.integers(*nt_range))
-        tris = (Triangle * nt)()
-        nm, tw, th = 5, int(rng.integers(1, 5)), int(rng.integers(1, 5))
-        qm = (C.c_int * nt)(*[int(x) for x in (rng.choice([0, 1, 2], nt) if opaque else rng.integers(0, nm, nt))])
-        for k in range(nt):
-            A = rng.uniform([-2, -2, -5], [2, 2, -1.5])
-            e = rng.normal(size=(2, 3)) * 0.5
-            tris[k].A, tris[k].B, tris[k].C = Vec3(*A), Vec3(*(A + e[0])), Vec3(*(A + e[1]))
-            tris[k].uvA, tris[k].uvB, tris[k].uvC = (UV(*rng.uniform(-2, 2, 2)) for _ in range(3))
-        mats = (Material * (nm * tw * th))()
-        for k in range(nm * tw * th):
-            mats[k] = scenes.material(_zero_some(rng, tuple(rng.uniform(0, 1, 3)), zeros), (0, 0, 0), 0.0, 0.0,
-                                      1.0 if opaque else float(rng.choice([0.0, 0.5, 1.0, 0.7])), 0.0)
-        mesh = (tris, qm, mats, tw, th, nm)
-    cam_o, cam_t = rng.uniform(-0.5, 0.5, 3), rng.uniform([-1, -1, -4], [1, 1, -2])
-    vfov = float(rng.uniform(40, 100))
-    W, H = int(rng.integers(8, 33)), int(rng.integers(6, 25))
-    spp_b = (int(rng.integers(1, 6)), int(rng.integers(0, bounce_hi)))
-    use_ao, ao, rseed = bool(rng.random() < 0.4), float(rng.uniform(0.5, 3.5)), int(rng.integers(0, 2 ** 40))
-    aperture, focus = tuple(rng.choice([0.0, 0.0, 1.0, 2.0], 2)), float(rng.uniform(1, 5))
-    compat, chunks_d = int(rng.integers(0, 2)), int(rng.choice([1, 1, 2, 3]))
-    if far:
-        # main()'s coordinate regime (camera at |o| ~ 1000, main.c:300-301;
-        # sky sphere of radius 1e5, main.c:346): the whole scene scaled by s
-        # and moved by T, then enclosed by an emissive radius-1e5 sky
-        s, T = float(rng.uniform(50, 2000)), rng.uniform(-1000, 1000, 3)
-        for k in range(ns):
-            sph[k].center = Vec3(*(T + s * np.array(sph[k].center.tolist())))
-            sph[k].radius = s * sph[k].radius
-        if mesh is not None:
-            for t in mesh[0]:
-                t.A, t.B, t.C = (Vec3(*(T + s * np.array(P.tolist()))) for P in (t.A, t.B, t.C))
-        cam_o, cam_t = T + s * cam_o, T + s * cam_t
-        focus *= s
-        sky = (Sphere * (ns + 1))()
-        for k in range(ns):
-            sky[k] = sph[k]
-        sky[ns].center, sky[ns].radius = Vec3(0.0, 0.0, 0.0), 1e5
-        sky[ns].mat = scenes.material((0, 0, 0), scenes.SKY, 1.0, 0.0, 1.0, 1.0)
-        sph = sky
-    bundle = helpers.SceneBundle(sph, mesh)
-    cam = tipe_rt.init_camera(tuple(cam_o), tuple(cam_t), (0, 1, 0), vfov, 4.0 / 3.0)
-    p = helpers.params(W, H, *spp_b, use_ao=use_ao, ao=ao, seed=rseed, cam=cam, aperture=aperture, focus=focus,
-                       compat=compat, chunks=chunks_d)
-    if chunks is not None:
-        p.spp_chunks = chunks
-        p.nbRayonParPixel = max(p.nbRayonParPixel, chunks)
-    if spp is not None:
-        p.nbRayonParPixel = spp
-    return bundle, p
 
 
 @pytest.mark.parametrize("seed", range(64))

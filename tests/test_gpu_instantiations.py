@@ -20,32 +20,11 @@ import pytest
 
 import helpers
 import tipe_rt
+from gpu_driver import assert_stack_bound_holds, render_and_compare
+from kernel_cases import ALPHA_KERNEL, OVERRIDE_KERNEL, _nature, one_transparent, override_tree, prm
 from tipe_rt import scenes
 
-from test_gpu_bvh_fallback import render_and_compare
-
 pytestmark = pytest.mark.gpu
-
-
-def one_transparent(alpha):
-    """README box plus one extra small sphere of the given alpha in view."""
-    extra = [((0.1, -0.9, -1.8), 0.3, scenes.material((0.8, 0.8, 0.8), alpha=alpha, ior=1.5))]
-    return helpers.SceneBundle(scenes.cornell_spheres(extra=extra))
-
-
-P = dict(W=40, H=30, spp=8, bounces=6)
-
-
-def prm(**kw):
-    q = dict(P)
-    q.update(kw)
-    return helpers.params(q["W"], q["H"], q["spp"], q["bounces"], chunks=4)
-
-
-# alpha of the extra sphere -> the kernel (tests/test_launch_plan.py checks the same pairs on the CPU)
-ALPHA_KERNEL = {0.5: "render_kernel_q<QB=-1>", 0.99: "render_kernel_q<QB=-1>", 0.00005: "render_kernel_q<QB=-1>",
-                0.0: "render_kernel_q<QB=-1>", 0.9900001: "render_kernel_q<QB=-2>"}
-OVERRIDE_KERNEL = "render_kernel_q<QB=3>"
 
 
 def test_opaque_sphere_scene_takes_qb_minus2():
@@ -84,22 +63,6 @@ def test_tree_scene_with_transparent_sphere_keeps_qb3():
     assert render_and_compare(bundle, p) == "render_kernel_q<QB=3>"
 
 
-def override_tree(mat_index):
-    """tri_material's material indices 3 and 4 force alpha 0.1 / 0.6 whatever
-    the texel holds: a tree whose first triangles use one of them is not
-    opaque.  The texel table gets entries up to that index (copies of
-    material 0), so the scene stays valid."""
-    tris, qm, mats, tw, th, nm = scenes.moved(scenes.load_tree_fixture(), scenes.TREE_MOVE)
-    from tipe_rt.types import Material
-    n_new = max(nm, mat_index + 1)
-    mats2 = (Material * (n_new * tw * th))()
-    for k in range(n_new * tw * th):
-        mats2[k] = mats[k] if k < nm * tw * th else mats[0]
-    for k in range(0, len(tris), 7):
-        qm[k] = mat_index
-    return helpers.SceneBundle(scenes.cornell_spheres(), (tris, qm, mats2, tw, th, n_new))
-
-
 @pytest.mark.parametrize("mat_index", [3, 4])
 def test_tree_with_override_material_keeps_qb3(mat_index):
     p = helpers.params(40, 30, 6, 8, use_ao=True, chunks=4)
@@ -112,7 +75,6 @@ def test_bvh_stack_bound_holds_on_the_gpu(scene):
     kernel plan_render picks for the tree (rt.h RT_CNT_BVH_STACK_OVER):
     the C4 tree (deep-tree queue kernel, 24 entries), the 100-triangle sweep
     mesh and mineways (606 triangles), over a whole frame with AO."""
-    from test_gpu_parity import assert_stack_bound_holds
     if scene == "tree":
         bundle = helpers.tree_scene()
     elif scene == "mineways":
@@ -132,38 +94,14 @@ def test_bvh_stack_bound_holds_on_the_gpu(scene):
     assert c[tipe_rt.types.RT_CNT_BVH_NODES] > 0          # the tree was walked
 
 
-def _nature(opaque, far_z=4e4):
-    """RTX_MAP/nature plus one 0.1-unit triangle at z = far_z, behind the
-    camera: the triangles' coordinate bound R_b becomes 4e4, which widens
-    every box's padding, and the tree's exact stack bound becomes 26."""
-    from tipe_rt.types import Triangle
-    import ctypes as C
-    tris, qm, mats, tw, th, nm = scenes.nature_mesh()
-    n = len(tris)
-    t2, q2 = (Triangle * (n + 1))(), (C.c_int * (n + 1))()
-    C.memmove(t2, tris, C.sizeof(Triangle) * n)
-    C.memmove(q2, qm, C.sizeof(C.c_int) * n)
-    for P, xy in ((t2[n].A, (0.0, 0.0)), (t2[n].B, (0.1, 0.0)), (t2[n].C, (0.0, 0.1))):
-        P.e[0], P.e[1], P.e[2] = xy[0], xy[1], far_z
-    q2[n] = 0
-    if opaque:                          # every texel at alpha 1, no material index 3 / 4 override
-        for k in range(len(mats)):
-            mats[k].alpha = 1.0
-        for k in range(n + 1):
-            if q2[k] in (3, 4):
-                q2[k] = 0
-    return helpers.SceneBundle(scenes.main_spheres(), (t2, q2, mats, tw, th, nm))
-
-
 @pytest.mark.parametrize("opaque", [False, True])
 def test_tree_with_stack_bound_above_24_keeps_the_queue_kernel(opaque):
-    """A tree whose exact stack bound is 26 (> 24, _nature above).  The
+    """A tree whose exact stack bound is 26 (> 24, kernel_cases._nature).  The
     non-opaque deep-tree kernel has 32 LDS stack entries (kStackQN; 38 KiB
     per block, still 4 blocks per CU), so it takes such trees -- an opaque
     one too, instead of the 24-entry OPQ kernel -- rather than the fixed
     grid; every push stays inside (RT_CNT_BVH_STACK_OVER == 0), bit for bit
     vs the oracle."""
-    from test_gpu_parity import assert_stack_bound_holds
     bundle = _nature(opaque)
     p = helpers.params(32, 24, 4, 10, chunks=4, cam=helpers.camera_of(scenes.NATURE_CAMERA))
     assert render_and_compare(bundle, p) == "render_kernel_q<QB=3>"

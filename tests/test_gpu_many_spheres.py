@@ -12,9 +12,8 @@ import numpy as np
 import pytest
 
 import helpers
+from gpu_driver import check_parity
 from tipe_rt import scenes
-from tipe_rt.types import Sphere, Vec3
-from test_gpu_parity import check_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -24,24 +23,20 @@ def _many(n, seed=5):
     lights / diffuse balls in front of the camera, the rest far behind it."""
     base = scenes.cornell_spheres()
     rng = np.random.default_rng(seed)
-    sph = (Sphere * n)()
-    for k in range(len(base)):
-        sph[k] = base[k]
-    for k in range(len(base), n):
-        if k < len(base) + 400:
-            c = rng.uniform([-1.5, -1.2, -4.0], [1.5, 1.2, -1.5])
-            r = float(rng.uniform(0.02, 0.08))
-        else:                                   # behind the camera, each still tested by every cast
-            c = rng.uniform([-50, -50, 5], [50, 50, 60])
-            r = float(rng.uniform(0.01, 0.3))
-        kind = k % 3
-        m = scenes.material(tuple(rng.uniform(0, 1, 3)),
-                            tuple(rng.uniform(0.2, 1, 3)) if kind == 1 else (0, 0, 0),
-                            2.0 if kind == 1 else 0.0, 0.9 if kind == 2 else 0.0, 1.0, 1.0)
-        sph[k].center = Vec3(*c)
-        sph[k].radius = r
-        sph[k].mat = m
-    return helpers.SceneBundle(sph)
+
+    def rows():
+        for k in range(len(base), n):
+            if k < len(base) + 400:
+                c = rng.uniform([-1.5, -1.2, -4.0], [1.5, 1.2, -1.5])
+                r = float(rng.uniform(0.02, 0.08))
+            else:                                   # behind the camera, each still tested by every cast
+                c = rng.uniform([-50, -50, 5], [50, 50, 60])
+                r = float(rng.uniform(0.01, 0.3))
+            kind = k % 3
+            yield c, r, scenes.material(tuple(rng.uniform(0, 1, 3)),
+                                        tuple(rng.uniform(0.2, 1, 3)) if kind == 1 else (0, 0, 0),
+                                        2.0 if kind == 1 else 0.0, 0.9 if kind == 2 else 0.0, 1.0, 1.0)
+    return helpers.SceneBundle(helpers.spheres_plus(base, rows()))
 
 
 @pytest.mark.parametrize("n", [65534, 65535, 70001])

@@ -13,9 +13,9 @@ import pytest
 
 import helpers
 import tipe_rt
+from gpu_driver import check_parity
+from helpers import stress_rays
 from tipe_rt import scenes
-from tipe_rt.types import Sphere, Vec3
-from test_gpu_parity import check_parity, _stress_rays
 
 pytestmark = pytest.mark.gpu
 
@@ -28,13 +28,7 @@ AXIS /= np.linalg.norm(AXIS)
 
 
 def bundle_of(rows):
-    """rows: (center, radius, Material)."""
-    arr = (Sphere * len(rows))()
-    for k, (c, r, m) in enumerate(rows):
-        arr[k].center = Vec3(*[float(x) for x in c])
-        arr[k].radius = r
-        arr[k].mat = m
-    return helpers.SceneBundle(arr)
+    return helpers.SceneBundle(helpers.sphere_array(rows))
 
 
 def readme_rows(rows, wall_refl=None):
@@ -104,7 +98,7 @@ def test_verify_sphere_pass(name, mode, monkeypatch):
     if mode != "auto":
         monkeypatch.setenv("RT_CAND_MERGE", mode)
     b = bundle_of(scene_rows(name))
-    rays = _stress_rays(b.spheres, 300_000, 11)
+    rays = stress_rays(b.spheres, 300_000, 11)
     # rays along the camera axis and through pairs of centres: lines that cross two spheres
     rng = np.random.default_rng(12)
     C_ = np.array([[s.center.e[0], s.center.e[1], s.center.e[2]] for s in b.spheres])

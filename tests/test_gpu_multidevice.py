@@ -21,6 +21,7 @@ import pytest
 
 import helpers
 import tipe_rt
+from gpu_driver import PLANES, assert_same, assert_same_frame, device_planes
 
 pytestmark = pytest.mark.gpu
 
@@ -63,13 +64,11 @@ def test_render_gather_slots_bitexact(slots, tile_rows, chunks, scene):
             p = helpers.params(W, H, 8, 6, chunks=chunks)
         p.gather = PEER                    # slots on one GPU: peer copies (RCCL has one rank per GPU)
         ref = helpers.oracle_render(bundle, p)
-        planes = torch.full((4, H, W, 3), -2.0, dtype=torch.float64, device="cuda:0")
+        planes = device_planes(H, W, fill=-2.0)
         st = torch.cuda.current_stream().cuda_stream
-        tipe_rt.render_gather_async(bundle.scene, p, tile_rows, *[planes[k].data_ptr() for k in range(4)], stream=st)
+        tipe_rt.render_gather_async(bundle.scene, p, tile_rows, *[t.data_ptr() for t in planes], stream=st)
         torch.cuda.synchronize()
-        got = planes.cpu().numpy()
-        for k, name in enumerate(("canva", "albedo", "normal", "radiance")):
-            assert (got[k] == ref[name]).all(), name
+        assert_same_frame([t.cpu().numpy() for t in planes], ref)
         assert tipe_rt.last_gather_transport().startswith("peer:")
     finally:
         lib.rt_shutdown()
@@ -90,12 +89,12 @@ def test_render_gather_canva_only_and_repeat():
         st = torch.cuda.current_stream().cuda_stream
         outs = []
         for _ in range(2):
-            c = torch.full((H, W, 3), -1.0, dtype=torch.float64, device="cuda:0")
+            c, = device_planes(H, W, n=1)
             tipe_rt.render_gather_async(bundle.scene, p, 1, c.data_ptr(), stream=st)
             outs.append(c)
         torch.cuda.synchronize()
         for c in outs:
-            assert (c.cpu().numpy() == ref["canva"]).all()
+            assert_same(c.cpu().numpy(), ref["canva"], "canva")
     finally:
         lib.rt_shutdown()
         tipe_rt.check(lib.rt_init(0, None))
@@ -125,13 +124,11 @@ def test_rccl_gather_one_device_bitexact(scene, planes_wanted):
         ref = helpers.oracle_render(bundle, p)
         st = torch.cuda.current_stream().cuda_stream
         for _ in range(2):
-            planes = torch.full((4, H, W, 3), -2.0, dtype=torch.float64, device="cuda:0")
+            planes = device_planes(H, W, fill=-2.0)
             ptrs = [planes[k].data_ptr() if k < planes_wanted else None for k in range(4)]
             tipe_rt.render_gather_async(bundle.scene, p, 1, *ptrs, stream=st)
             torch.cuda.synchronize()
-            got = planes.cpu().numpy()
-            for k, name in enumerate(("canva", "albedo", "normal", "radiance")[:planes_wanted]):
-                assert (got[k] == ref[name]).all(), name
+            assert_same_frame([t.cpu().numpy() for t in planes], ref, planes=PLANES[:planes_wanted])
             assert tipe_rt.last_gather_transport().startswith("rccl: ncclGather"), tipe_rt.last_gather_transport()
     finally:
         lib.rt_shutdown()
@@ -171,11 +168,11 @@ def test_gather_async_explicit_locals():
     locs = [torch.zeros((per_rank, W, 3), dtype=torch.float64, device="cuda:0") for _ in range(world)]
     for r in range(world):
         tipe_rt.render_async(ds, p, tipe_rt.cyclic_tiling(H, k, r, world), locs[r].data_ptr(), stream=st)
-    full = torch.full((H, W, 3), -1.0, dtype=torch.float64, device="cuda:0")
+    full, = device_planes(H, W, n=1)
     tipe_rt.gather_async([0] * world, [t.data_ptr() for t in locs], k, per_rank, W, H, 0, full.data_ptr(), st)
     torch.cuda.synchronize()
     ds.close()
-    assert (full.cpu().numpy() == ref["canva"]).all()
+    assert_same(full.cpu().numpy(), ref["canva"], "canva")
 
 
 def test_gather_rejects_short_geometry():
@@ -218,7 +215,7 @@ def test_rt_init_rejects_invisible_device_and_keeps_list():
         bundle = helpers.cornell()
         p = helpers.params(16, 12, 2, 4)
         canva, _, _ = tipe_rt.render_rows(bundle.scene, p)       # still device 0 alone
-        assert (canva == helpers.oracle_render(bundle, p)["canva"]).all()
+        assert_same(canva, helpers.oracle_render(bundle, p)["canva"], "canva")
     finally:
         tipe_rt.check(lib.rt_init(0, None))
 
@@ -251,7 +248,7 @@ def test_render_gather_distinct_devices_bitexact(peer_env, gather):
     code = r'''
 import ctypes as C, sys
 sys.path[:0] = %r
-import torch, helpers, tipe_rt
+import torch, helpers, tipe_rt, gpu_driver
 lib = tipe_rt.lib()
 tipe_rt.check(lib.rt_init(2, (C.c_int * 2)(0, 1)))
 bundle = helpers.pyramid_scene()
@@ -259,15 +256,13 @@ W, H = 52, 41
 p = helpers.params(W, H, 8, 6, chunks=4)
 p.gather = %d
 ref = helpers.oracle_render(bundle, p)
-planes = torch.full((4, H, W, 3), -2.0, dtype=torch.float64, device="cuda:0")
-tipe_rt.render_gather_async(bundle.scene, p, 1, *[planes[k].data_ptr() for k in range(4)],
+planes = gpu_driver.device_planes(H, W, fill=-2.0)
+tipe_rt.render_gather_async(bundle.scene, p, 1, *[t.data_ptr() for t in planes],
                             stream=torch.cuda.current_stream().cuda_stream)
 torch.cuda.synchronize()
-got = planes.cpu().numpy()
-ok = all((got[k] == ref[n]).all() for k, n in enumerate(("canva", "albedo", "normal", "radiance")))
-st = lib.rt_peer_access(0, 1)
 print("TRANSPORT", tipe_rt.last_gather_transport())
-print("RESULT", int(ok), st)
+gpu_driver.assert_same_frame([t.cpu().numpy() for t in planes], ref)      # a mismatch ends the child with its message
+print("RESULT", 1, lib.rt_peer_access(0, 1))
 ''' % ([os.path.join(ROOT, "tests"), os.path.join(ROOT, "tipe-raytracer_amd")], gather)
     env = dict(os.environ, RT_PEER_ACCESS=peer_env)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)

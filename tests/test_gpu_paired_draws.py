@@ -18,14 +18,12 @@ A camera inside the box that looks out of its open side: central pixels miss
 at the first cast of every sample (resolve_hit's miss, whose two adds of
 (0, 0, 0) the paired form does not make), outer pixels hit a wall sphere.
 """
-import numpy as np
 import pytest
 
 import helpers
-from tipe_rt import scenes
 
-from test_gpu_bvh_fallback import render_and_compare
-from test_gpu_queue_variants import TRANSPARENT, bundle_of
+from gpu_driver import render_and_compare
+from kernel_cases import TRANSPARENT, bundle_of
 
 pytestmark = pytest.mark.gpu
 

@@ -1,13 +1,17 @@
 """GPU parity: librt_hip.so (through the C-ABI) vs the CPU oracle in
-RT_RNG_PHILOX mode on identical seeded inputs.
+RT_RNG_PHILOX mode on identical seeded inputs.  First the device primitives
+(the portable math of oracle/pm_math.h, normalize, the sampler's phi, Philox)
+through rt_selftest_math and the rt_verify_* sweeps; then scene by scene:
+every kernel family on the README box, the textured and alpha meshes, the
+BVH's ties and deep walks, degenerate and 4K frames.  The bar for a frame
+(tests/gpu_driver.py check_parity) is BIT-EXACT equality of canva, albedo,
+normal and radiance.
 
-The kernel performs the reference's IEEE operations in the same order as the
-oracle, so the bar is BIT-EXACT equality of canva (8-bit resolve), albedo,
-normal and pre-gamma radiance.  north_star's tolerance (per-channel RMSE
-<= 1e-4 on float accumulation) is asserted as well, as the outer bound.
+The rt_verify_* fast-path stress runs, the counters and the other entry
+points have files of their own: test_gpu_verify_paths.py,
+test_gpu_counters.py, test_gpu_entry_points.py.
 """
 import ctypes as C
-import threading
 
 import numpy as np
 import pytest
@@ -15,75 +19,10 @@ import pytest
 import helpers
 import oracle_ffi
 import tipe_rt
-from tipe_rt.types import ThreadData, Sphere, Triangle, Material
+from gpu_driver import assert_same_frame, check_parity, gpu_counts, gpu_render
+from tipe_rt.types import Triangle, Material
 
 pytestmark = pytest.mark.gpu
-
-RMSE_TOL = 1e-4   # north_star: per-channel RMSE on identical seeds
-
-
-def gpu_render(bundle, p, tiling=None, radiance=True):
-    """Device path: rt_scene_upload + rt_render_async into torch buffers."""
-    import torch
-    W, H = p.largeur_image, p.hauteur_image
-    if tiling is None:
-        tiling = tipe_rt.band_tiling(0, H - 1)
-    rows = tiling.n_tiles * tiling.tile_rows
-    dev = torch.device("cuda:0")
-    bufs = [torch.full((rows, W, 3), -1.0, dtype=torch.float64, device=dev) for _ in range(4)]
-    ds = tipe_rt.DeviceScene(bundle.scene, 0)
-    stream = torch.cuda.current_stream().cuda_stream
-    tipe_rt.render_async(ds, p, tiling, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(),
-                         bufs[3].data_ptr() if radiance else None, stream)
-    torch.cuda.synchronize()
-    ds.close()
-    return [b.cpu().numpy() for b in bufs]
-
-
-def gpu_counts(bundle, p):
-    """rt_count_async over the whole frame: the RT_NCOUNTERS event totals."""
-    import torch
-    ds = tipe_rt.DeviceScene(bundle.scene, 0)
-    d = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device="cuda:0")
-    tipe_rt.count_async(ds, p, tipe_rt.band_tiling(0, p.hauteur_image - 1), d.data_ptr(),
-                        torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    ds.close()
-    return [int(x) for x in d.cpu()]
-
-
-def assert_stack_bound_holds(bundle, p):
-    """Every BVH push of the frame's walks stays inside the LDS stack of the
-    kernel that renders the tree (rt.h RT_CNT_BVH_STACK_OVER == 0), i.e.
-    the host's stack bound (rt_bvh.cpp) covers the kernel's push rule."""
-    c = gpu_counts(bundle, p)
-    assert c[tipe_rt.types.RT_CNT_BVH_STACK_OVER] == 0, c
-    return c
-
-
-def assert_same(gpu, ref, what):
-    """Bit-for-bit equal values; NaN must sit at the same places (payloads
-    may differ: x86 and gfx950 produce different default NaNs)."""
-    assert gpu.shape == ref.shape, what
-    diff = np.argwhere((gpu != ref) & ~(np.isnan(gpu) & np.isnan(ref)))
-    if len(diff):
-        j, i, c = diff[0]
-        raise AssertionError("%s: %d mismatching values; first at row %d col %d ch %d: gpu %r oracle %r" %
-                             (what, len(diff), j, i, c, gpu[j, i, c], ref[j, i, c]))
-
-
-def check_parity(bundle, p, nthreads=1):
-    ref = helpers.oracle_render(bundle, p, nthreads=nthreads)
-    canva, alb, nrm, rad = gpu_render(bundle, p)
-    fin = ~np.isnan(ref["radiance"])               # NaN radiance: the reference's own (e.g. AO 0)
-    assert (np.isnan(rad) == ~fin).all()
-    assert (helpers.rmse_per_channel(np.where(fin, rad, 0), np.where(fin, ref["radiance"], 0)) <= RMSE_TOL).all()
-    assert (helpers.rmse_per_channel(canva / 255.0, ref["canva"] / 255.0) <= RMSE_TOL).all()
-    assert_same(canva, ref["canva"], "canva")
-    assert_same(rad, ref["radiance"], "radiance")
-    assert_same(alb, ref["albedo"], "albedo")
-    assert_same(nrm, ref["normal"], "normal")
-    return ref
 
 
 # ---- device primitives ------------------------------------------------------
@@ -218,15 +157,6 @@ def test_device_atan2_matches_oracle():
     assert (got.view(np.uint64) == want.view(np.uint64)).all()
 
 
-def test_sky_mode_last_sphere():
-    """main.c:64-71's commented-out sky branch (RT_SKY_LAST_SPHERE): the last
-    sphere shows sphere_uvmapping's texel as emission."""
-    bundle = helpers.sky_scene()
-    ref = check_parity(bundle, helpers.params(48, 36, 6, 5, sky_mode=1))
-    off = check_parity(bundle, helpers.params(48, 36, 6, 5, sky_mode=0))
-    assert not (ref["canva"] == off["canva"]).all()     # the sky changes the image
-
-
 def test_device_philox_matches_oracle():
     o = oracle_ffi.oracle()
     rng = np.random.default_rng(3)
@@ -239,6 +169,15 @@ def test_device_philox_matches_oracle():
         out = (C.c_uint * 4)()
         o.oracle_philox(ctr, key, out)
         assert list(out) == [int(x) for x in got[i]]
+
+
+def test_sky_mode_last_sphere():
+    """main.c:64-71's commented-out sky branch (RT_SKY_LAST_SPHERE): the last
+    sphere shows sphere_uvmapping's texel as emission."""
+    bundle = helpers.sky_scene()
+    ref = check_parity(bundle, helpers.params(48, 36, 6, 5, sky_mode=1))
+    off = check_parity(bundle, helpers.params(48, 36, 6, 5, sky_mode=0))
+    assert not (ref["canva"] == off["canva"]).all()     # the sky changes the image
 
 
 # ---- full renders -------------------------------------------------------------
@@ -303,27 +242,6 @@ def test_synthetic_sweep_scenes_bitexact(ns, nt):
     bundle = helpers.SceneBundle(sph, mesh)
     check_parity(bundle, helpers.params(32, 24, 4, 6, chunks=2))
     check_parity(bundle, helpers.params(24, 18, 3, 5, use_ao=True, ao=2.5, compat=0))
-
-
-def test_task_queue_kernel_cyclic_tiles():
-    """The queue kernel on a rank's cyclic row tiles (multi-GPU layout)."""
-    import torch
-    bundle = helpers.cornell()
-    W, H, k, world = 40, 30, 2, 3
-    p = helpers.params(W, H, 8, 5, chunks=4)
-    ref = helpers.oracle_render(bundle, p)
-    ds = tipe_rt.DeviceScene(bundle.scene, 0)
-    stream = torch.cuda.current_stream().cuda_stream
-    per_rank = tipe_rt.cyclic_tiling(H, k, 0, world).n_tiles
-    gathered = torch.zeros((world, per_rank * k, W, 3), dtype=torch.float64, device="cuda:0")
-    for r in range(world):
-        t = tipe_rt.cyclic_tiling(H, k, r, world)
-        tipe_rt.render_async(ds, p, t, gathered[r].data_ptr(), stream=stream)
-    full = torch.zeros((H, W, 3), dtype=torch.float64, device="cuda:0")
-    tipe_rt.assemble_async(gathered.data_ptr(), world, k, per_rank * k, W, H, full.data_ptr(), stream)
-    torch.cuda.synchronize()
-    ds.close()
-    assert (full.cpu().numpy() == ref["canva"]).all()
 
 
 def test_spp_chunks_only_move_the_last_bits():
@@ -544,14 +462,7 @@ def test_bvh_grazing_grid_deep_traversal():
     cam = tipe_rt.init_camera((0.0, -0.9, -0.6), (0.0, -0.935, -3.0), (0, 1, 0), 40.0, 4.0 / 3.0)
     check_parity(bundle, helpers.params(32, 24, 4, 6, cam=cam))
     check_parity(bundle, helpers.params(24, 18, 2, 5, cam=cam, use_ao=True, ao=2.0))
-    import torch
-    p = helpers.params(32, 24, 4, 6, cam=cam)
-    ds = tipe_rt.DeviceScene(bundle.scene, 0)
-    d_cnt = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device="cuda:0")
-    tipe_rt.count_async(ds, p, tipe_rt.band_tiling(0, 23), d_cnt.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    ds.close()
-    c = d_cnt.cpu().numpy()
+    c = gpu_counts(bundle, helpers.params(32, 24, 4, 6, cam=cam))
     T = tipe_rt.types
     print("grazing grid: node visits / cast", c[T.RT_CNT_BVH_NODES] / c[T.RT_CNT_CASTS],
           "triangle tests / cast", c[T.RT_CNT_BVH_TRI_TESTS] / c[T.RT_CNT_CASTS])
@@ -559,84 +470,12 @@ def test_bvh_grazing_grid_deep_traversal():
     assert c[T.RT_CNT_BVH_NODES] > 2 * c[T.RT_CNT_CASTS]
 
 
-def adversarial_sphere_scene():
-    """Sphere pairs the candidate pass cannot separate (spheres_closest):
-    an exact duplicate (equal t: the reference keeps the first), a sphere
-    1e-12 larger than its neighbour, spheres touching each other and the
-    floor, a tiny sphere and a huge far one.  Each must fall back to the
-    exact scan or be resolved exactly."""
-    m = tipe_rt.scenes.material
-    extra = [
-        ((0.3, 0.2, -2.5), 0.3, m((1, 0, 0))),
-        ((0.3, 0.2, -2.5), 0.3, m((0, 1, 0), refl=0.5)),                 # duplicate: first wins
-        ((-0.4, 0.1, -2.0), 0.25, m((0, 0, 1))),
-        ((-0.4, 0.1, -2.0), 0.25 + 1e-12, m((1, 1, 0))),                  # 1e-12 apart
-        ((0.0, -0.5, -1.8), 0.5, m((0.9, 0.9, 0.9), refl=0.9)),          # touches the floor (y = -1)
-        ((0.5, -0.5, -1.8), 0.5, m((0.2, 0.8, 0.5))),        # touches the previous one
-        ((0.05, 0.3, -1.2), 1e-4, m((1, 1, 1), (1, 1, 1), 3.0)),         # tiny emitter
-        ((0.0, 0.0, -2e4), 1e4, m((0.5, 0.5, 0.5))),                     # huge, far
-    ]
-    return helpers.cornell(extra)
-
-
-def _stress_rays(spheres, n, seed):
-    """Rays that stress the candidate pass's bound: origins on sphere surfaces
-    (as a bounce leaves them), directions near tangent at 1e-3..1e-12, rays
-    aimed at silhouettes (disc ~ 0), unnormalised directions, far origins."""
-    rng = np.random.default_rng(seed)
-    C_ = np.array([[s.center.e[0], s.center.e[1], s.center.e[2]] for s in spheres])
-    R_ = np.array([s.radius for s in spheres])
-
-    def unit(v):
-        return v / np.linalg.norm(v, axis=-1, keepdims=True)
-    m = n // 5
-    k = rng.integers(0, len(R_), m)
-    # 1. surface origins, random and near-tangent directions
-    nrm = unit(rng.normal(size=(m, 3)))
-    o1 = C_[k] + R_[k, None] * nrm
-    tan = unit(np.cross(nrm, rng.normal(size=(m, 3))))
-    eps = rng.choice([0.0, 1e-3, 1e-6, 1e-9, 1e-12], m)[:, None] * rng.choice([-1.0, 1.0], (m, 1))
-    d1 = np.where(rng.random((m, 1)) < 0.5, unit(rng.normal(size=(m, 3))), tan + eps * nrm)
-    # 2. silhouette rays from random box points
-    o2 = rng.uniform([-1, -1, -4], [1, 1, 0.5], (m, 3))
-    k2 = rng.integers(0, len(R_), m)
-    w = C_[k2] - o2
-    perp = unit(np.cross(w, rng.normal(size=(m, 3))))
-    d2 = (C_[k2] + R_[k2, None] * perp * (1 + rng.choice([0, 1e-9, -1e-9, 1e-14], m)[:, None])) - o2
-    # 3. random rays, 4. unnormalised, 5. far origins
-    o3 = rng.uniform([-1, -1, -4], [1, 1, 0.5], (m, 3))
-    d3 = unit(rng.normal(size=(m, 3)))
-    d4 = unit(rng.normal(size=(m, 3))) * 10.0 ** rng.uniform(-3, 3, (m, 1))
-    o5 = unit(rng.normal(size=(m, 3))) * rng.uniform(10, 2000, (m, 1))
-    d5 = unit(rng.uniform(-1, 1, (m, 3)) - o5)
-    o = np.concatenate([o1, o2, o3, o3, o5])
-    d = np.concatenate([d1, d2, d3, d4, d5])
-    return np.concatenate([o, d], axis=1)
-
-
-@pytest.mark.parametrize("which", ["cornell", "adversarial"])
-def test_sphere_candidate_pass_stress(which):
-    """5M stress rays: the candidate pass (with its exact fallback) returns the
-    exact scan's winner and distance bit for bit on every ray."""
-    bundle = helpers.cornell() if which == "cornell" else adversarial_sphere_scene()
-    rays = _stress_rays(bundle.spheres, 5_000_000, 7 if which == "cornell" else 8)
-    fb, bad = tipe_rt.verify_sphere_pass(bundle.scene, rays)
-    assert bad == 0
-    assert fb < len(rays) // 2
-
-
 def test_sphere_candidate_pass_adversarial():
-    import torch
-    bundle = adversarial_sphere_scene()
+    bundle = helpers.adversarial_sphere_scene()
     check_parity(bundle, helpers.params(48, 36, 8, 6))
     check_parity(bundle, helpers.params(32, 24, 4, 6, use_ao=True, ao=2.5, compat=0))
-    p = helpers.params(48, 36, 4, 6)
-    ds = tipe_rt.DeviceScene(bundle.scene, 0)
-    d_cnt = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device="cuda:0")
-    tipe_rt.count_async(ds, p, tipe_rt.band_tiling(0, 35), d_cnt.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    ds.close()
-    assert d_cnt[tipe_rt.types.RT_CNT_EXACT_RESCANS].item() > 0      # the fallback scan ran
+    c = gpu_counts(bundle, helpers.params(48, 36, 4, 6))
+    assert c[tipe_rt.types.RT_CNT_EXACT_RESCANS] > 0      # the fallback scan ran
 
 
 @pytest.mark.parametrize("W,H", [(1, 1), (1, 5), (5, 1), (2, 2), (17, 3)])
@@ -652,220 +491,4 @@ def test_c5_4k_frame_pyramid_one_spp():
     bundle = helpers.pyramid_scene()
     p = helpers.params(3840, 2880, 1, 6)
     ref = helpers.oracle_render(bundle, p, nthreads=16)
-    canva, alb, nrm, rad = gpu_render(bundle, p)
-    assert_same(canva, ref["canva"], "canva")
-    assert_same(rad, ref["radiance"], "radiance")
-    assert_same(alb, ref["albedo"], "albedo")
-    assert_same(nrm, ref["normal"], "normal")
-
-
-def test_counters_match_oracle():
-    import torch
-    bundle = helpers.pyramid_scene()
-    p = helpers.params(32, 24, 8, 6, use_ao=True)
-    ref = helpers.oracle_render(bundle, p, counters=True)["counters"]
-    ds = tipe_rt.DeviceScene(bundle.scene, 0)
-    d_cnt = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device="cuda:0")
-    with tipe_rt.reference_counts():
-        tipe_rt.count_async(ds, p, tipe_rt.band_tiling(0, 23), d_cnt.data_ptr(),
-                            torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-    got = d_cnt.cpu().numpy().astype(np.uint64)
-    ds.close()
-    k = tipe_rt.types.RT_CNT_EXACT_RESCANS           # GPU-only diagnostic
-    assert list(got[:k]) == list(ref[:k]), dict(zip(tipe_rt.COUNTER_NAMES, zip(got, ref)))
-    assert got[k] <= got[tipe_rt.types.RT_CNT_CASTS] // 1000   # candidate pass almost never ambiguous
-
-
-def _counts(bundle, p, rows):
-    import torch
-    ds = tipe_rt.DeviceScene(bundle.scene, 0)
-    d_cnt = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device="cuda:0")
-    tipe_rt.count_async(ds, p, tipe_rt.band_tiling(0, rows - 1), d_cnt.data_ptr(),
-                        torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    ds.close()
-    return d_cnt.cpu().numpy()
-
-
-@pytest.mark.parametrize("scene,ao", [("cornell", False), ("cornell", True), ("pyramid", True), ("tree", True)])
-def test_zero_throughput_exit(scene, ao):
-    """Paths end once rayColor == 0 (rt_set_zero_throughput_exit): frames are
-    bit-identical with the exit on and off and to the oracle (which never
-    exits), and the exit only removes casts."""
-    bundle = {"cornell": helpers.cornell, "pyramid": helpers.pyramid_scene, "tree": helpers.tree_scene}[scene]()
-    p = helpers.params(32, 24, 8, 6, use_ao=ao, ao=2.5, compat=0)
-    check_parity(bundle, p)
-    on = gpu_render(bundle, p)
-    with tipe_rt.reference_counts():
-        off = gpu_render(bundle, p)
-        ref_cnt = _counts(bundle, p, 24)
-    for a, b in zip(on, off):
-        assert_same(a, b, "exit on vs off")
-    cnt = _counts(bundle, p, 24)
-    T = tipe_rt.types
-    assert cnt[T.RT_CNT_SAMPLES] == ref_cnt[T.RT_CNT_SAMPLES]
-    assert cnt[T.RT_CNT_CASTS] < ref_cnt[T.RT_CNT_CASTS]
-    print(scene, "ao" if ao else "", "casts per sample", ref_cnt[T.RT_CNT_CASTS] / ref_cnt[0], "->",
-          cnt[T.RT_CNT_CASTS] / cnt[0])
-
-
-def test_zero_throughput_exit_gated_off():
-    """A material beyond the exit's bound (emission strength 1e200 > 2^100:
-    the host cannot rule out em overflowing to inf, and inf * 0 is NaN) or
-    AO_intensity outside (0, 1000] turns the exit off: the counts are then
-    the reference's."""
-    spheres = tipe_rt.scenes.cornell_spheres()
-    spheres[3].mat.emissionStrength = 1e200
-    bundle = helpers.SceneBundle(spheres)
-    p = helpers.params(16, 12, 4, 6)
-    check_parity(bundle, p)
-    ref = helpers.oracle_render(bundle, p, counters=True)["counters"]
-    cnt = _counts(bundle, p, 12)
-    assert cnt[tipe_rt.types.RT_CNT_CASTS] == ref[tipe_rt.types.RT_CNT_CASTS]
-    bundle = helpers.cornell()
-    p = helpers.params(16, 12, 4, 6, use_ao=True, ao=2000.0, compat=0)
-    check_parity(bundle, p)
-    ref = helpers.oracle_render(bundle, p, counters=True)["counters"]
-    cnt = _counts(bundle, p, 12)
-    assert cnt[tipe_rt.types.RT_CNT_CASTS] == ref[tipe_rt.types.RT_CNT_CASTS]
-
-
-# ---- boundary behaviour --------------------------------------------------------
-def test_render_rows_host_api_band():
-    bundle = helpers.cornell()
-    p = helpers.params(48, 36, 4, 5)
-    ref = helpers.oracle_render(bundle, p)
-    canva = np.full((36, 48, 3), -7.0)
-    alb = np.full((36, 48, 3), -7.0)
-    nrm = np.full((36, 48, 3), -7.0)
-    tipe_rt.check(tipe_rt.lib().rt_render_rows(C.byref(bundle.scene), C.byref(p), 20, 9, canva.ctypes.data,
-                                               alb.ctypes.data, nrm.ctypes.data))
-    assert (canva[9:21] == ref["canva"][9:21]).all()
-    assert (alb[9:21] == ref["albedo"][9:21]).all() and (nrm[9:21] == ref["normal"][9:21]).all()
-    untouched = np.ones(36, bool)
-    untouched[9:21] = False
-    assert (canva[untouched] == -7.0).all()       # only the named rows are written
-
-
-def test_cyclic_tiles_assemble_to_full_frame():
-    import torch
-    bundle = helpers.cornell()
-    W, H, k, world = 40, 30, 4, 3
-    p = helpers.params(W, H, 4, 5)
-    ref = helpers.oracle_render(bundle, p)
-    ds = tipe_rt.DeviceScene(bundle.scene, 0)
-    stream = torch.cuda.current_stream().cuda_stream
-    per_rank = tipe_rt.cyclic_tiling(H, k, 0, world).n_tiles
-    gathered = torch.zeros((world, per_rank * k, W, 3), dtype=torch.float64, device="cuda:0")
-    for r in range(world):
-        t = tipe_rt.cyclic_tiling(H, k, r, world)
-        tipe_rt.render_async(ds, p, t, gathered[r].data_ptr(), stream=stream)
-    full = torch.zeros((H, W, 3), dtype=torch.float64, device="cuda:0")
-    tipe_rt.assemble_async(gathered.data_ptr(), world, k, per_rank * k, W, H, full.data_ptr(), stream)
-    torch.cuda.synchronize()
-    ds.close()
-    assert (full.cpu().numpy() == ref["canva"]).all()
-
-
-def test_fill_canva_pthread_dropin():
-    """rt_fill_canva takes main.c's ThreadData; 4 threads on disjoint bands."""
-    bundle = helpers.cornell()
-    W, H = 40, 30
-    p = helpers.params(W, H, 4, 5)
-    ref = helpers.oracle_render(bundle, p)
-    canva, alb, nrm = (np.zeros((H, W, 3)) for _ in range(3))
-    tds = []
-    bands = [(29, 22), (21, 15), (14, 8), (7, 0)]
-    for hi, lo in bands:
-        td = ThreadData()
-        td.start_row, td.end_row = hi, lo
-        td.canva = C.cast(canva.ctypes.data, C.POINTER(tipe_rt.Vec3))
-        td.albedo_tab = C.cast(alb.ctypes.data, C.POINTER(tipe_rt.Vec3))
-        td.normal_tab = C.cast(nrm.ctypes.data, C.POINTER(tipe_rt.Vec3))
-        td.cam = p.cam
-        td.largeur_image, td.hauteur_image = W, H
-        td.nbRayonParPixel, td.nbRebondMax = 4, 5
-        td.total_pixels = W * H
-        td.sphere_list = C.cast(bundle.spheres, C.POINTER(Sphere))
-        td.nbSpheres = len(bundle.spheres)
-        td.focus_distance = 3
-        tds.append(td)
-    res = []
-    ths = [threading.Thread(target=lambda t=t: res.append(tipe_rt.lib().rt_fill_canva(C.byref(t)))) for t in tds]
-    for t in ths:
-        t.start()
-    for t in ths:
-        t.join()
-    assert all(r is None for r in res), tipe_rt.lib().rt_last_error()
-    assert (canva == ref["canva"]).all() and (alb == ref["albedo"]).all() and (nrm == ref["normal"]).all()
-
-
-def test_invalid_arguments_fail_loudly():
-    bundle = helpers.cornell()
-    p = helpers.params(8, 6, 0, 5)
-    canva = np.zeros((6, 8, 3))
-    rc = tipe_rt.lib().rt_render_rows(C.byref(bundle.scene), C.byref(p), 5, 0, canva.ctypes.data, None, None)
-    assert rc == tipe_rt.RT_EINVAL and b"nbRayonParPixel" in tipe_rt.lib().rt_last_error()
-    p = helpers.params(8, 6, 1, 5, rng=tipe_rt.RT_RNG_GLIBC)
-    rc = tipe_rt.lib().rt_render_rows(C.byref(bundle.scene), C.byref(p), 5, 0, canva.ctypes.data, None, None)
-    assert rc == tipe_rt.RT_EUNSUPPORTED
-
-
-@pytest.mark.parametrize("tw,th", [(16, 16), (3, 1), (64, 5), (1, 1)])
-def test_texel_map_fast_path_stress(tw, th):
-    """rt_verify_texel_map: the affine uv fast path (rt_scene_prep.cpp tri_uv_affine
-    + tri_texel_affine) against the reference's barycentric operations on
-    random triangles (scales 1e-3..1e2, far from the origin, skinny ones),
-    random and grid-aligned uvs (boundaries through structured points, uv
-    repeats, negatives), and points in and around each triangle (barycentric
-    coordinates on a 1/16 grid and random ones, off the plane by up to the
-    triangle's size): no point may get another texel, and the fast path must
-    decide almost every point."""
-    from tipe_rt.scenes import material
-    rng = np.random.default_rng(1000 + tw * 7 + th)
-    total_fast = total = 0
-    for scene_i in range(12):
-        nt = 32
-        tris = (Triangle * nt)()
-        A = np.zeros((nt, 3)); B = np.zeros((nt, 3)); Cc = np.zeros((nt, 3))
-        for k in range(nt):
-            s = 10.0 ** rng.uniform(-3, 2)
-            c = rng.uniform(-1, 1, 3) * (s * 10.0 ** rng.uniform(0, 3))
-            a, b, cc = c + rng.normal(size=3) * s, c + rng.normal(size=3) * s, c + rng.normal(size=3) * s
-            if k % 8 == 7:                                   # skinny: C near the segment AB
-                cc = a + (b - a) * rng.uniform(0.2, 0.8) + rng.normal(size=3) * s * 1e-3
-            A[k], B[k], Cc[k] = a, b, cc
-            for name, v in (("A", a), ("B", b), ("C", cc)):
-                getattr(tris[k], name).e[:] = tuple(v)
-            if k % 2:                                        # grid-aligned uvs: multiples of 1/tw, 1/th
-                uvs = [(rng.integers(-2 * tw, 3 * tw) / tw, rng.integers(-2 * th, 3 * th) / th) for _ in range(3)]
-            else:
-                uvs = [tuple(rng.uniform(-3, 6, 2)) for _ in range(3)]
-            for name, (u, v) in zip(("uvA", "uvB", "uvC"), uvs):
-                getattr(tris[k], name).u, getattr(tris[k], name).v = u, v
-            tris[k].mat = material((0.5, 0.5, 0.5))
-        qm = (C.c_int * nt)(*([0] * nt))
-        mats = (Material * (tw * th))()
-        for i in range(tw * th):
-            mats[i] = material((0.5, 0.5, 0.5))
-        scene = tipe_rt.make_scene(tipe_rt.scenes.cornell_spheres(), tris, qm, mats, tw, th, 1)
-        m = 1 << 16
-        tri = rng.integers(0, nt, m)
-        grid = rng.integers(-3, 20, (m, 2)) / 16.0
-        rnd = rng.uniform(-0.2, 1.2, (m, 2))
-        bc = np.where((np.arange(m) % 2 == 0)[:, None], grid, rnd)
-        b0, b1 = bc[:, 0], bc[:, 1]
-        b2 = 1.0 - b0 - b1
-        P = b0[:, None] * A[tri] + b1[:, None] * B[tri] + b2[:, None] * Cc[tri]
-        N = np.cross(B[tri] - A[tri], Cc[tri] - A[tri])
-        nl = np.linalg.norm(N, axis=1)[:, None]
-        size = np.max(np.abs(np.stack([B[tri] - A[tri], Cc[tri] - A[tri]])), axis=(0, 2))[:, None]
-        off = np.where((np.arange(m) % 3 == 0)[:, None], 0.0, rng.uniform(-1, 1, (m, 1)) * size)
-        P = P + off * N / np.where(nl > 0, nl, 1.0)
-        fast, bad = tipe_rt.verify_texel_map(scene, P, tri)
-        assert bad == 0, (scene_i, fast, bad)
-        total_fast += fast
-        total += m
-    print("texel map fast path: %d of %d points" % (total_fast, total))
-    assert total_fast >= 0.5 * total, (total_fast, total)
+    assert_same_frame(gpu_render(bundle, p), ref)

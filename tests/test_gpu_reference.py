@@ -27,6 +27,7 @@ import pytest
 import composition_cases as cc
 import helpers
 import oracle_ffi
+from gpu_driver import gpu_render
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gpu_reference.json")
 with open(GOLDEN) as f:
@@ -59,14 +60,12 @@ def test_fixture_covers_every_case():
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", NAMES)
 def test_gpu_matches_reference_code(name):
-    from test_gpu_parity import gpu_render
     bundle, p = _scene(name)
-    canva, alb, nrm, rad = gpu_render(bundle, p)
-    _check(name, dict(canva=canva, albedo=alb, normal=nrm, radiance=rad))
+    got, kernel = gpu_render(bundle, p, kernel=True)
+    _check(name, dict(zip(cc.PLANES, got)))
     want = cc.PHILOX_BY_NAME[name].kernel
     if want is not None:
-        import tipe_rt
-        assert tipe_rt.last_render_kernel() == want
+        assert kernel == want
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -20,7 +20,7 @@ import pytest
 import helpers
 import tipe_rt
 from tipe_rt.types import ThreadData, Sphere
-from test_gpu_parity import check_parity, gpu_render, assert_same
+from gpu_driver import PLANES, assert_same, assert_same_frame, check_parity, gpu_render
 
 pytestmark = pytest.mark.gpu
 
@@ -48,11 +48,7 @@ def test_queue_kernel_c5_4k_frame():
     bundle = helpers.pyramid_scene()
     p = helpers.params(3840, 2880, 4, 6, chunks=4)
     ref = helpers.oracle_render(bundle, p, nthreads=ORACLE_THREADS)
-    canva, alb, nrm, rad = gpu_render(bundle, p)
-    assert_same(canva, ref["canva"], "canva")
-    assert_same(rad, ref["radiance"], "radiance")
-    assert_same(alb, ref["albedo"], "albedo")
-    assert_same(nrm, ref["normal"], "normal")
+    assert_same_frame(gpu_render(bundle, p), ref)
 
 
 def test_bvh_kernel_c4_band():
@@ -61,17 +57,8 @@ def test_bvh_kernel_c4_band():
     bundle = helpers.tree_scene()
     p = helpers.params(1200, 900, 2, 8, use_ao=True)
     ref = helpers.oracle_render(bundle, p, row_hi=463, row_lo=400, nthreads=ORACLE_THREADS)
-    import torch
-    rows = 64
-    bufs = [torch.full((rows, 1200, 3), -1.0, dtype=torch.float64, device="cuda:0") for _ in range(4)]
-    ds = tipe_rt.DeviceScene(bundle.scene, 0)
-    tipe_rt.render_async(ds, p, tipe_rt.band_tiling(400, 463), *[b.data_ptr() for b in bufs],
-                         torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    ds.close()
-    got = [b.cpu().numpy() for b in bufs]
-    for k, name in enumerate(("canva", "albedo", "normal", "radiance")):
-        assert_same(got[k], ref[name][400:464], name)
+    got = gpu_render(bundle, p, tipe_rt.band_tiling(400, 463))
+    assert_same_frame(got, [ref[name][400:464] for name in PLANES])
 
 
 def test_bvh_queue_kernel_c4_band():
@@ -80,17 +67,8 @@ def test_bvh_queue_kernel_c4_band():
     bundle = helpers.tree_scene()
     p = helpers.params(1200, 900, 4, 8, use_ao=True, chunks=4)
     ref = helpers.oracle_render(bundle, p, row_hi=463, row_lo=400, nthreads=ORACLE_THREADS)
-    import torch
-    rows = 64
-    bufs = [torch.full((rows, 1200, 3), -1.0, dtype=torch.float64, device="cuda:0") for _ in range(4)]
-    ds = tipe_rt.DeviceScene(bundle.scene, 0)
-    tipe_rt.render_async(ds, p, tipe_rt.band_tiling(400, 463), *[b.data_ptr() for b in bufs],
-                         torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    ds.close()
-    got = [b.cpu().numpy() for b in bufs]
-    for k, name in enumerate(("canva", "albedo", "normal", "radiance")):
-        assert_same(got[k], ref[name][400:464], name)
+    got = gpu_render(bundle, p, tipe_rt.band_tiling(400, 463))
+    assert_same_frame(got, [ref[name][400:464] for name in PLANES])
 
 
 def test_bvh_queue_kernel_c4_full_frame():
@@ -138,7 +116,7 @@ def test_render_rows_auto_chunks_reaches_queue_kernel():
     p = helpers.params(64, 48, 40, 6, chunks=tipe_rt.RT_SPP_CHUNKS_AUTO)
     ref = helpers.oracle_render(bundle, p)
     canva, alb, nrm = tipe_rt.render_rows(bundle.scene, p)
-    assert (canva == ref["canva"]).all() and (alb == ref["albedo"]).all() and (nrm == ref["normal"]).all()
+    assert_same_frame([canva, alb, nrm], ref, planes=PLANES[:3])
     # AUTO at 40 spp is 32 slices: not the strict running sum
     strict = helpers.oracle_render(bundle, helpers.params(64, 48, 40, 6, chunks=1))
     assert not (strict["radiance"] == ref["radiance"]).all()
@@ -155,10 +133,10 @@ def test_render_rows_scene_cache_tracks_content():
     a = tipe_rt.render_rows(bundle.scene, p)[0]
     b = tipe_rt.render_rows(bundle.scene, p)[0]
     assert (a == b).all()
-    assert (a == helpers.oracle_render(bundle, p)["canva"]).all()
+    assert_same(a, helpers.oracle_render(bundle, p)["canva"], "canva")
     spheres[9].center.e[0] = 0.1                       # same pointer, new contents (mirror sphere moved)
     c = tipe_rt.render_rows(bundle.scene, p)[0]
-    assert (c == helpers.oracle_render(bundle, p)["canva"]).all()
+    assert_same(c, helpers.oracle_render(bundle, p)["canva"], "canva after the move")
     assert not (c == a).all()
     assert lib.rt_scene_cache_clear() >= 2
 
@@ -186,11 +164,11 @@ def test_render_rows_two_device_slots(planes):
                 tipe_rt.check(lib.rt_render_rows(C.byref(bundle.scene), C.byref(p), hi, lo, canva.ctypes.data,
                                                  alb.ctypes.data if alb is not None else None,
                                                  nrm.ctypes.data if nrm is not None else None))
-                assert (canva[lo:hi + 1] == ref["canva"][lo:hi + 1]).all()
+                names = PLANES[:3] if planes == "all" else PLANES[:1]
+                got = [a[lo:hi + 1] for a in (canva, alb, nrm)[:len(names)]]
+                assert_same_frame(got, [ref[k][lo:hi + 1] for k in names], planes=names)
                 assert (canva[:lo] == -3.0).all() and (canva[hi + 1:] == -3.0).all()
                 if planes == "all":
-                    assert (alb[lo:hi + 1] == ref["albedo"][lo:hi + 1]).all()
-                    assert (nrm[lo:hi + 1] == ref["normal"][lo:hi + 1]).all()
                     for a in (alb, nrm):
                         assert (a[:lo] == -3.0).all() and (a[hi + 1:] == -3.0).all()
     finally:
@@ -215,8 +193,8 @@ def test_render_rows_large_band_threaded_scatter(ndev):
         planes = [np.full((H, W, 3), -5.0) for _ in range(3)]
         tipe_rt.check(lib.rt_render_rows(C.byref(bundle.scene), C.byref(p), hi, lo,
                                          *[a.ctypes.data for a in planes]))
-        for a, key in zip(planes, ("canva", "albedo", "normal")):
-            assert (a[lo:hi + 1] == ref[key][lo:hi + 1]).all(), key
+        assert_same_frame([a[lo:hi + 1] for a in planes], [ref[k][lo:hi + 1] for k in PLANES[:3]], planes=PLANES[:3])
+        for a, key in zip(planes, PLANES):
             assert (a[:lo] == -5.0).all() and (a[hi + 1:] == -5.0).all(), key
     finally:
         lib.rt_shutdown()
@@ -260,7 +238,7 @@ def test_fill_canva_twelve_threads_auto_chunks():
     for t in ths:
         t.join()
     assert all(r is None for r in res), lib.rt_last_error()
-    assert (canva == ref["canva"]).all() and (alb == ref["albedo"]).all() and (nrm == ref["normal"]).all()
+    assert_same_frame([canva, alb, nrm], ref, planes=PLANES[:3])
     # strict fill_canva order on request
     prev = lib.rt_set_fill_spp_chunks(1)
     try:
@@ -269,7 +247,7 @@ def test_fill_canva_twelve_threads_auto_chunks():
         lib.rt_fill_canva(C.byref(td))
         strict = helpers.oracle_render(bundle, helpers.params(W, H, S, B, chunks=1, compat=0))
         lo, hi = td.end_row, td.start_row
-        assert (canva[lo:hi + 1] == strict["canva"][lo:hi + 1]).all()
-        assert (alb[lo:hi + 1] == strict["albedo"][lo:hi + 1]).all()
+        assert_same_frame([canva[lo:hi + 1], alb[lo:hi + 1]], [strict[k][lo:hi + 1] for k in PLANES[:2]],
+                          "strict order:", PLANES[:2])
     finally:
         lib.rt_set_fill_spp_chunks(tipe_rt.RT_SPP_CHUNKS_AUTO)

@@ -10,7 +10,7 @@ the plans; a `facts` section gives the scalars the plan depends on directly, so
 every boundary is hit exactly.
 
 The scene cases are the (scene, params, kernel name) triples the GPU tests
-assert on the device, imported from their modules.  The scalar cases follow
+assert on the device, from tests/kernel_cases.py.  The scalar cases follow
 the rule in plan_render's comment: a narrow tree takes QB 4 (14 stack entries)
 when its bound fits, no origin is far and it is shallow or has no 64-byte
 nodes; else QB 3 over the 64-byte nodes (32 entries; OPQ, 24, when every
@@ -26,10 +26,7 @@ import pytest
 
 import composition_cases as cc
 import helpers
-import test_gpu_big_mesh as big_mesh
-import test_gpu_bvh_fallback as fallback
-import test_gpu_instantiations as inst
-import test_gpu_queue_variants as variants
+import kernel_cases as kc
 from tipe_rt import scenes
 from tipe_rt.types import RT_SEM_CUDA
 
@@ -105,32 +102,32 @@ def kernels(checker, bundle, params):
 # ---- scenes -> kernel names, as the GPU tests assert them ------------------------------------------
 
 @pytest.mark.parametrize("sky", [False, True], ids=["nosky", "sky"])
-@pytest.mark.parametrize("variant", list(variants.VARIANTS))
+@pytest.mark.parametrize("variant", list(kc.VARIANTS))
 def test_queue_variant_scenes(checker, variant, sky):
-    name, extra, mesh = variants.VARIANTS[variant]
-    bundle = variants.bundle_of(extra, mesh(), sky)
-    plans = run(checker, scene_text(bundle) + "".join(params_text(variants.variant_params(sky, ao))
+    name, extra, mesh = kc.VARIANTS[variant]
+    bundle = kc.bundle_of(extra, mesh(), sky)
+    plans = run(checker, scene_text(bundle) + "".join(params_text(kc.variant_params(sky, ao))
                                                       for ao in (False, True)))
     assert [pl["name"] for pl in plans] == [name, name]
     assert [(pl["sky"], pl["ao"]) for pl in plans] == [(int(sky), 0), (int(sky), 1)]
 
 
-@pytest.mark.parametrize("alpha", list(inst.ALPHA_KERNEL))
+@pytest.mark.parametrize("alpha", list(kc.ALPHA_KERNEL))
 def test_sphere_alpha_thresholds(checker, alpha):
-    assert kernels(checker, inst.one_transparent(alpha), [inst.prm()]) == [inst.ALPHA_KERNEL[alpha]]
+    assert kernels(checker, kc.one_transparent(alpha), [kc.prm()]) == [kc.ALPHA_KERNEL[alpha]]
 
 
 @pytest.mark.parametrize("mat_index", [3, 4])
 def test_override_material_tree(checker, mat_index):
     p = helpers.params(40, 30, 6, 8, use_ao=True, chunks=4)
-    assert kernels(checker, inst.override_tree(mat_index), [p]) == [inst.OVERRIDE_KERNEL]
+    assert kernels(checker, kc.override_tree(mat_index), [p]) == [kc.OVERRIDE_KERNEL]
 
 
 @pytest.mark.parametrize("opaque", [False, True])
 def test_tree_with_stack_bound_26(checker, opaque):
-    """test_gpu_instantiations.py's _nature: above OPQ's 24 entries, within QB 3's 32."""
+    """kernel_cases._nature: above OPQ's 24 entries, within QB 3's 32."""
     p = helpers.params(32, 24, 4, 10, chunks=4, cam=helpers.camera_of(scenes.NATURE_CAMERA))
-    pl, = run(checker, scene_text(inst._nature(opaque)) + params_text(p))
+    pl, = run(checker, scene_text(kc._nature(opaque)) + params_text(p))
     assert (pl["name"], pl["bvh_stack"], pl["stack_cap"]) == ("render_kernel_q<QB=3>", 26, 32)
 
 
@@ -140,9 +137,9 @@ def test_reference_cases(checker, name):
     assert kernels(checker, bundle, [p]) == [cc.PHILOX_BY_NAME[name].kernel]
 
 
-@pytest.mark.parametrize("name", list(fallback.FALLBACK))
+@pytest.mark.parametrize("name", list(kc.FALLBACK))
 def test_trees_without_binary16_nodes(checker, name):
-    scene, params, kernel = fallback.FALLBACK[name]
+    scene, params, kernel = kc.FALLBACK[name]
     assert kernels(checker, scene(), [params()]) == [kernel]
 
 
@@ -151,12 +148,12 @@ def test_boundary_between_narrow_and_wide(checker):
     and above 0x8000 triangles no narrow tree takes the queue kernel (test_gpu_big_mesh.py)."""
     mesh = scenes.heightfield_mesh(182, 1, 0.25, scenes.README_FLOOR)
     ps = [helpers.params(32, 24, 1, 4), helpers.params(32, 24, 4, 4, chunks=4)]
-    wide = helpers.SceneBundle(scenes.cornell_spheres(), big_mesh.truncated(mesh, 65536))
+    wide = helpers.SceneBundle(scenes.cornell_spheres(), helpers.mesh_of(mesh, 65536))
     plans = run(checker, scene_text(wide) + "".join(params_text(p) for p in ps))
-    assert [pl["name"] for pl in plans] == [big_mesh.BVH32, big_mesh.QB5]
+    assert [pl["name"] for pl in plans] == [kc.BVH32, kc.QB5]
     assert [(pl["wide"], pl["stack_cap"]) for pl in plans] == [(1, 48), (1, 32)]
     assert plans[0]["bvh_stack"] <= 32
-    narrow = helpers.SceneBundle(scenes.cornell_spheres(), big_mesh.truncated(mesh, 65535))
+    narrow = helpers.SceneBundle(scenes.cornell_spheres(), helpers.mesh_of(mesh, 65535))
     plans = run(checker, scene_text(narrow) + "".join(params_text(p) for p in ps))
     assert [pl["name"] for pl in plans] == ["render_kernel<BVH>"] * 2
     assert [(pl["wide"], pl["stack_cap"], pl["bvh_stack"]) for pl in plans] == [(0, 48, 1 << 30)] * 2

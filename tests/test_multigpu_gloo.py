@@ -8,7 +8,7 @@ bit-identical to a single-rank render for every rank count: pixels are
 independent and the Philox stream is keyed by the global pixel index.
 
 Rendering uses the CPU oracle (test infrastructure); on the GPU box the same
-flow runs through librt_hip.so (test_gpu_parity / bench.py)."""
+flow runs through librt_hip.so (test_gpu_entry_points / bench.py)."""
 import os
 
 import numpy as np

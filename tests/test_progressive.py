@@ -10,7 +10,7 @@ import pytest
 
 import helpers
 import tipe_rt
-from test_gpu_parity import gpu_render, assert_same
+from gpu_driver import assert_same, assert_same_frame, device_planes, gpu_render
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +35,7 @@ def progressive(bundle, p_full, batches, chunks=1, checkpoint_after=None):
             sums.fill_(float("nan"))
             sums.copy_(torch.from_numpy(saved))
     assert off == S
-    planes = [torch.full((H, W, 3), -1.0, dtype=torch.float64, device=dev) for _ in range(4)]
+    planes = device_planes(H, W)
     tipe_rt.resolve_async(sums.data_ptr(), p_full, S, tiling, *(t.data_ptr() for t in planes), stream=stream)
     torch.cuda.synchronize()
     ds.close()
@@ -48,8 +48,7 @@ def test_batches_equal_one_shot(batches):
     p = helpers.params(40, 30, 12, 6)
     one = gpu_render(bundle, p)
     got = progressive(bundle, p, batches, checkpoint_after=0)
-    for g, o, name in zip(got, one, ["canva", "albedo", "normal", "radiance"]):
-        assert_same(g, o, name)
+    assert_same_frame(got, one)
     ref = helpers.oracle_render(bundle, p)
     assert_same(got[0], ref["canva"], "canva vs oracle")
 

@@ -1,14 +1,14 @@
 #!/bin/bash
 # Exhaustive CPU check of sqrt_rcp_near1 + div_core0 (rt_device_math.h): every
 # double in [1 - 2^-18, 1 + 2^-18] (5.2e10 values) in 8 slices, with the
-# program tests/test_near1_sqrt.py builds from the header's own source.
+# program tests/near1_check.py builds from the header's own source.
 # Usage: bash tools/check_near1.sh   (about 4 minutes on 8 cores)
 set -e -o pipefail
 D=$(mktemp -d)
 python3 - "$D" <<'EOF'
 import pathlib, sys
 sys.path.insert(0, "tests")
-import test_near1_sqrt as t
+import near1_check as t
 print(t.build(pathlib.Path(sys.argv[1])))
 EOF
 python3 - "$D" <<'EOF'

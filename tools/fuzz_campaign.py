@@ -2,8 +2,8 @@
 families of tests/test_gpu_fuzz.py (random scenes with 0-24 bounces; exact-zero
 colours on the queue kernel; CUDA semantics; 100-400 triangle BVH scenes on a
 1-3 block queue grid; the opaque instantiations; r06: main()'s far coordinate
-regime, with and without 100-400 triangle trees), bit for bit (check_parity:
-canva, albedo, normal, radiance).
+regime, with and without 100-400 triangle trees), bit for bit (tests/gpu_driver.py
+check_parity: canva, albedo, normal, radiance) on tests/helpers.py random_scene.
 Prints one line per scene; writes a JSON summary.
 Usage: python3 tools/fuzz_campaign.py OUT.json [scenes per family] [first seed]"""
 import json
@@ -18,8 +18,8 @@ sys.path.insert(0, os.path.join(ROOT, "tipe-raytracer_amd"))
 
 import tipe_rt  # noqa: E402
 from tipe_rt import scenes  # noqa: E402
-from test_gpu_fuzz import random_scene  # noqa: E402
-from test_gpu_parity import check_parity  # noqa: E402
+from gpu_driver import check_parity  # noqa: E402
+from helpers import random_scene  # noqa: E402
 
 
 def family_cases(name, seed):
