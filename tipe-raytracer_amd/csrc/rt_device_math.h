@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "rt_shared_math.h"
+
 namespace rt {
 
 typedef const double __attribute__((address_space(4)))* cdptr;
@@ -93,47 +95,8 @@ __device__ __forceinline__ cdptr kcb()
 // Scalar load of constant i from a base b = kcb().
 #define KCV(b, i) ((b)[(i)])
 
-// ---- Philox4x32-10 (Random123 / rocrand_philox4x32_10 engine) -------------
-struct Philox {
-    uint32_t w0, w1, w2, w3;
-};
-
-// a ^ b ^ k in one VALU op: gfx950's v_bitop3_b32 with truth table 0x96
-// (three-input xor; k a wave-uniform SGPR)
-__device__ __forceinline__ uint32_t xor3_s(uint32_t a, uint32_t b, uint32_t k)
-{
-#if defined(__gfx950__)
-    uint32_t r;
-    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(r) : "v"(a), "v"(b), "s"(k));
-    return r;
-#else
-    return a ^ b ^ k;                  // other targets: the compiler's own xor chain
-#endif
-}
-
-template <bool UNIFORM_KEY = true>
-__device__ __forceinline__ Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                                uint32_t k0, uint32_t k1)
-{
-    if (UNIFORM_KEY) asm volatile("" : "+s"(k0), "+s"(k1));   // key schedule in place (SALU), not hoisted
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        // one v_mad_u64_u32 yields both halves of each 32x32 product; the
-        // round's two xors with the key are one v_bitop3_b32 each
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        uint32_t n0, n2;
-        if (UNIFORM_KEY) {
-            n0 = xor3_s((uint32_t)(p1 >> 32), c1, k0);
-            n2 = xor3_s((uint32_t)(p0 >> 32), c3, k1);
-        } else {
-            n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-            n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        }
-        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return Philox{c0, c1, c2, c3};
-}
+// ---- Philox4x32-10: rt_shared_math.h (Philox, xor3_s, philox4x32_10 and the
+// per-task head of a block), which a CPU check compiles too ----------------
 
 // Draw stream of one (pixel, sample): draw n = word (n & 3) of
 // philox(ctr = {n >> 2, 0, pixel, sample}, key = seed) >> 1   (rt.h)

@@ -430,6 +430,13 @@ void render_kernel_q(const KParams kp)
     QPath<SKY, AOM, QB < 0, QB == -2 || OPQ, QIR, QB == 0, PD> L;
     L.init(acc);
     uint32_t kw2 = 0, kw3 = 0;       // (PD) the kept words of the sample's current block
+    // (PD) A block's counter is {block, 0, pixel, sample} and the pixel is the
+    // task's: the lane keeps the head of its task's blocks (rt_shared_math.h
+    // philox_head), made when it takes the task, in three LDS words of its own
+    // (the block cache's column is unused here), and step 4 starts each block
+    // from them.  A lane without a task draws nothing and reads none of them.
+    __shared__ uint32_t head_lds[PD ? 3 * 256 : 1];
+    uint32_t* head = head_lds + (PD ? threadIdx.x : 0);
 #if RT_DIAG_STALE == 2
     diag_cnt()[0] = 0u;
     diag_cnt()[256] = 0u;
@@ -526,7 +533,7 @@ void render_kernel_q(const KParams kp)
             }
         } else if (QB < 0 && L.state == SM_CAST) {          // sphere-only scenes: no triangle scan
             Cnt cnt;
-            L.win = cast_spheres<false, false, !SKY && AOM != AO_ON, true>(kp, L.o, L.cast_dir(), L.best, cnt);
+            L.win = cast_spheres<false, false, !SKY && AOM != AO_ON, true, PD>(kp, L.o, L.cast_dir(), L.best, cnt);
             L.kind = L.win >= 0 ? HIT_SPHERE : HIT_NONE;
             L.state = SM_RESOLVE;
         } else if (L.state == SM_CAST) {
@@ -538,8 +545,18 @@ void render_kernel_q(const KParams kp)
         // ---- 2. the hit, up to the next direction --------------------------
         int role = ROLE_NONE;
         QHit H;
-        H.hn = v3(0, 0, 0);
-        H.rs = 0.0;
+        if (PD) {
+            // No defaults: H.hn and H.rs are read by bounce lanes alone (step 4's
+            // else branch and finish_bounce), and resolve_hit sets both on every
+            // lane it gives ROLE_BOUNCE.  The empty asm defines the four values
+            // here, where the zeros were written, without an instruction: left
+            // undefined instead, their registers are allocated elsewhere and the
+            // kernel needs 107 VGPRs (profiles/round_trims/README.md).
+            asm volatile("" : "=v"(H.hn.x), "=v"(H.hn.y), "=v"(H.hn.z), "=v"(H.rs));
+        } else {
+            H.hn = v3(0, 0, 0);
+            H.rs = 0.0;
+        }
         H.refr = H.hole = false;
         if (L.state == SM_RESOLVE) role = L.resolve_hit(kp, acc, H, st.n);
         RT_PHASE(2);
@@ -601,9 +618,16 @@ void render_kernel_q(const KParams kp)
                     L.state = SM_DONE;
                 } else if (e[1] != 0xffffffffu) {  // else a padding row: the lane takes its next task next round
                     qidx = e[0];
-                    pixel = e[1];
+                    if constexpr (PD) {
+                        const PhiloxHead h = philox_head(e[1], K->key0);
+                        head[0] = h.c1;
+                        head[256] = h.hi;
+                        head[512] = h.lo;
+                    } else {
+                        pixel = e[1];
+                    }
                     g = (int)e[2];
-                    x = (int)(pixel - e[2] * (unsigned)K->W);
+                    x = (int)(e[1] - e[2] * (unsigned)K->W);
                     L.s = (int)e[3];
                     s1 = (int)e[4];
 #pragma unroll
@@ -642,7 +666,8 @@ void render_kernel_q(const KParams kp)
                 // sample never reads: bounce 0 opens block 1.
                 if (cam || (L.i & 1) == 0) {
                     const uint32_t bi = cam ? 0u : 1u + ((uint32_t)L.i >> 1);
-                    pblk = philox4x32_10(bi, 0u, pixel, (uint32_t)(kp.s_base + L.s), kp.key0, kp.key1);
+                    const PhiloxHead h{head[0], head[256], head[512]};
+                    pblk = philox4x32_10(bi, h, (uint32_t)(kp.s_base + L.s), kp.key0, kp.key1);
                     wa = pblk.w0;
                     wb = pblk.w1;
                     kw2 = pblk.w2;

@@ -43,6 +43,25 @@ __device__ __forceinline__ bool sphere_exact(double cx, double cy, double cz, do
     return false;
 }
 
+// (HB: the sphere-only queue kernel's paired-draw form) sphere_exact in half-b
+// units, rt_shared_math.h sphere_halfb with the exact cores above: fast is
+// halfb_fast_a(a) and rca = rcp_refined(a).  A lane outside its windows runs
+// the reference form as it stands, and without its fast path.
+struct HalfbCores {
+    __device__ __forceinline__ static double sqrt_in(double x) { return sqrt_core(x); }
+    __device__ __forceinline__ static double div_in(double x, double d, double rc) { return div_core(x, d, rc); }
+    __device__ __forceinline__ static bool reference(double cx, double cy, double cz, double r2, const V3 o, const V3 d,
+                                                     double a, double& t)
+    {
+        return sphere_exact<false>(cx, cy, cz, r2, o, d, 2 * a, 4 * a, false, 0.0, t);
+    }
+};
+__device__ __forceinline__ bool sphere_exact_hb(double cx, double cy, double cz, double r2, const V3 o, const V3 d,
+                                                double a, bool fast, double rca, double& t)
+{
+    return sphere_halfb<HalfbCores>(cx, cy, cz, r2, o, d, a, fast, rca, t);
+}
+
 // The reference's discriminant sign (sphere.h:24-25): COUNT statistics only.
 __device__ __forceinline__ bool disc_positive(const SphGeo& s, const V3 o, const V3 d, double four_a)
 {
@@ -53,7 +72,8 @@ __device__ __forceinline__ bool disc_positive(const SphGeo& s, const V3 o, const
 }
 
 // Exact reference scan over every sphere (main.c:59-78 with hit_sphere).
-template <bool CU>
+// HB: sphere_exact_hb, with a in two_a's place and rcp_refined(a) in rc2a's (cast_spheres).
+template <bool CU, bool HB = false>
 __device__ __forceinline__ int spheres_exact_scan(const KParams& kp, const V3 o, const V3 d, double two_a,
                                                   double four_a, bool fast, double rc2a, double& t_best)
 {
@@ -62,9 +82,11 @@ __device__ __forceinline__ int spheres_exact_scan(const KParams& kp, const V3 o,
     int win = -1;
     for (int k = 0; k < kp.ns_pad; ++k) {
         double tk;
-        if (sphere_exact<CU>(sg[4 * k], sg[4 * k + 1], sg[4 * k + 2], sg[4 * k + 3], o, d, two_a, four_a, fast,
-                             rc2a, tk) &&
-            tk < t) {
+        bool hit;
+        const double cx = sg[4 * k], cy = sg[4 * k + 1], cz = sg[4 * k + 2], r2 = sg[4 * k + 3];
+        if constexpr (HB) hit = sphere_exact_hb(cx, cy, cz, r2, o, d, two_a, fast, rc2a, tk);
+        else hit = sphere_exact<CU>(cx, cy, cz, r2, o, d, two_a, four_a, fast, rc2a, tk);
+        if (hit && tk < t) {
             t = tk;
             win = k;
         }
@@ -268,10 +290,14 @@ __device__ __forceinline__ void cand_second_tail(const CandRay& r, double h1, do
 // followed by a BVH walk, and rt_verify_sphere_pass; the BVH instantiations
 // keep the plain loop, which is right for any ns_merge -- with the flagged
 // loop their register allocation lost 0.7 % on C4)
-template <bool COUNT, bool CU, bool AMGM = false, bool MG = AMGM>
+// HB: the winner's test and the rescan in half-b units (sphere_exact_hb): the
+// caller passes a for two_a, rcp_refined(a) for rc2a and halfb_fast_a(a) for
+// fast, whose window implies the one the comments here assume (2a in 2^+-100).
+template <bool COUNT, bool CU, bool AMGM = false, bool MG = AMGM, bool HB = false>
 __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, const V3 d, double a, double two_a,
                                                double four_a, bool fast, double rc2a, double& t_best, Cnt& cnt)
 {
+    static_assert(!HB || (!COUNT && !CU), "half-b units: the reference thresholds, no counters");
     const cdptr sc = (cdptr)kp.sph_cand;
     const double INF = dinf();
     const double od = fma(o.z, d.z, fma(o.y, d.y, o.x * d.x));
@@ -482,12 +508,15 @@ __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, co
     if (!amb && bk >= 0) {
         const SphGeo s = kp.sph_slot[bk];    // the slot's sphere, and its index in the caller's list
         const int orig = kp.cand_orig[bk];
-        if (sphere_exact<CU>(s.cx, s.cy, s.cz, s.r2, o, d, two_a, four_a, fast, rc2a, t)) win = orig;
+        bool hit;
+        if constexpr (HB) hit = sphere_exact_hb(s.cx, s.cy, s.cz, s.r2, o, d, two_a, fast, rc2a, t);
+        else hit = sphere_exact<CU>(s.cx, s.cy, s.cz, s.r2, o, d, two_a, four_a, fast, rc2a, t);
+        if (hit) win = orig;
         else amb = true;     // cannot happen within the bound; stay exact anyway
     }
     if (amb) {               // exact reference scan for this ray
         if (COUNT) cnt.c[RT_CNT_EXACT_RESCANS] += 1;
-        win = spheres_exact_scan<CU>(kp, o, d, two_a, four_a, fast, rc2a, t);
+        win = spheres_exact_scan<CU, HB>(kp, o, d, two_a, four_a, fast, rc2a, t);
     }
     t_best = t;
     return win;

@@ -543,13 +543,15 @@ __device__ __forceinline__ bool cuda_bbox(const KParams& kp, const V3 o, const V
 
 // The sphere half of closest_hit (and the cast counters): the winner index
 // or -1, its t in best (+inf when none).
-template <bool COUNT, bool CU, bool AMGM = false, bool MG = AMGM>
+// HB: the exact tests in half-b units (rt_shared_math.h sphere_halfb), which read a where the
+// reference form reads 2a and 4a
+template <bool COUNT, bool CU, bool AMGM = false, bool MG = AMGM, bool HB = false>
 __device__ __forceinline__ int cast_spheres(const KParams& kp, const V3 o, const V3 d, double& best, Cnt& cnt)
 {
     const double a = dot(d, d);          // sphere.h:20 (same for every sphere)
-    const double two_a = 2 * a;          // sphere.h:27,36
+    const double two_a = HB ? a : 2 * a; // sphere.h:27,36
     const double four_a = 4 * a;         // sphere.h:24
-    const bool fast = two_a >= 0x1p-100 && two_a <= 0x1p100;
+    const bool fast = HB ? halfb_fast_a(a) : two_a >= 0x1p-100 && two_a <= 0x1p100;
     const double rc2a = rcp_refined(two_a);
     if (COUNT) {
         cnt.c[RT_CNT_CASTS] += 1;
@@ -557,7 +559,7 @@ __device__ __forceinline__ int cast_spheres(const KParams& kp, const V3 o, const
         cnt.c[RT_CNT_TRI_TESTS] += (unsigned long long)kp.nt;
         wave_slots(cnt, RT_CNT_CAST_LANE_SLOTS);
     }
-    int win = spheres_closest<COUNT, CU, AMGM, MG>(kp, o, d, a, two_a, four_a, fast, rc2a, best, cnt);
+    int win = spheres_closest<COUNT, CU, AMGM, MG, HB>(kp, o, d, a, two_a, four_a, fast, rc2a, best, cnt);
     return win;
 }
 

@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYM = sys.argv[1] if len(sys.argv) > 1 else "_ZN2rt15render_kernel_qILb0ELi0ELin2ELb0EEEvNS_7KParamsE"
 ASM = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "tipe-raytracer_amd", "rt_kernels_g.s")
 CSRC = os.path.join(ROOT, "tipe-raytracer_amd", "csrc")
-SRC = {f: os.path.join(CSRC, f) for f in ("rt_kernels.hip", "rt_device_math.h", "rt_vec.h", "rt_spheres.h",
+SRC = {f: os.path.join(CSRC, f) for f in ("rt_kernels.hip", "rt_device_math.h", "rt_shared_math.h", "rt_vec.h", "rt_spheres.h",
                                           "rt_triangles.h", "rt_shading.h", "rt_fixed_grid.h", "rt_queue.h")}
 KSRC = "rt_queue.h"          # the file that holds render_kernel_q and its phase markers
 
