@@ -16,7 +16,12 @@ when its bound fits, no origin is far and it is shallow or has no 64-byte
 nodes; else QB 3 over the 64-byte nodes (32 entries; OPQ, 24, when every
 material is opaque, the bound fits and no origin is far); else the fixed grid
 (48).  A wide tree takes QB 5 (32) or the fixed grid's wide kernel.
+
+Name and stack of a queue plan come from one table (rt_queue_variants.h), which
+the device code sizes its stacks by too; the checker prints it, and every queue
+plan any case here gets is compared with its row.
 """
+import functools
 import json
 import os
 import subprocess
@@ -85,6 +90,13 @@ def params_text(p=None, **kw):
     return "params " + " ".join("%s %r" % (k, float(v)) for k, v in d.items()) + " end\n"
 
 
+@functools.lru_cache(maxsize=None)
+def variants(checker):
+    """The queue kernel's table: [{qb, opq, name, stack}]."""
+    p = subprocess.run([checker, "variants"], capture_output=True, text=True, timeout=120, check=True)
+    return json.loads(p.stdout)["variants"]
+
+
 def run(checker, text, env=None):
     e = {k: v for k, v in os.environ.items() if k != "RT_PARTIAL_BUDGET"}
     e.update(env or {})
@@ -92,11 +104,27 @@ def run(checker, text, env=None):
     assert p.returncode == 0, p.stderr[-2000:]
     rec = json.loads(p.stdout.strip().splitlines()[-1])
     assert rec["rc"] == 0, rec
+    rows = {(v["qb"], v["opq"]): v for v in variants(checker)}
+    for pl in rec["plans"]:                                # every queue plan of every case is its table row
+        if pl["queue"]:
+            row = rows.get((pl["qb"], pl["opq"]))
+            assert row is not None, pl
+            assert (pl["name"], pl["stack_cap"]) == (row["name"], row["stack"]), (pl, row)
     return rec["plans"]
 
 
 def kernels(checker, bundle, params):
     return [pl["name"] for pl in run(checker, scene_text(bundle) + "".join(params_text(p) for p in params))]
+
+
+def test_queue_variant_table(checker):
+    """The seven (QB, OPQ) pairs, their reported names and their stack entries; run() holds every plan to them."""
+    table = sorted(variants(checker), key=lambda v: (v["qb"], v["opq"]))
+    assert [(v["qb"], v["opq"]) for v in table] == [(-2, 0), (-1, 0), (0, 0), (3, 0), (3, 1), (4, 0), (5, 0)]
+    names = [v["name"] for v in table]
+    assert names == ["render_kernel_q<QB=%s>" % s for s in ("-2", "-1", "0", "3", "3,OP", "4", "5")]
+    assert sorted(names) == sorted([name for name, _, _ in kc.VARIANTS.values()] + [kc.QB5])
+    assert [v["stack"] for v in table] == [0, 0, 0, 32, 24, 14, 32]
 
 
 # ---- scenes -> kernel names, as the GPU tests assert them ------------------------------------------

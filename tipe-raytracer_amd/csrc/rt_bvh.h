@@ -36,8 +36,9 @@ struct BvhNode4 {
 static_assert(sizeof(BvhNode4) == 128, "BvhNode4");
 
 constexpr int kStack4 = 48;         // kernel LDS stack entries (3 pushes per 4-wide level)
-// ... and of the queue kernel's instantiations (rt_triangles.h bvh_stack_q, bvh_stack_qw): QB 3 with every
-// material opaque, QB 3, QB 4, QB 5.  plan_render (rt_launch_plan.cpp) admits a tree by its exact bound.
+// ... and of the queue kernel's BVH families: QB_DEEP with every material opaque, QB_DEEP, QB_TOP, QB_WIDE.
+// rt_queue_variants.h gives each (QB, OPQ) pair its one, for the host's stack_cap and the device's arrays
+// (rt_triangles.h bvh_stack_for_q) alike.  plan_render (rt_launch_plan.cpp) admits a tree by its exact bound.
 constexpr int kStackQ = 24, kStackQN = 32, kStackQ4 = 14, kStackQW = 32;
 
 // The same 4-wide node in 64 bytes for the queue kernel (r03): binary16

@@ -16,7 +16,7 @@ __device__ __forceinline__ bool cuda_hit(const KParams& kp, const V3 o, const V3
 {
     double t;
     int idx;
-    const int kind = closest_hit<COUNT, BVH, true, false, SE>(kp, o, d, t, idx, cnt);
+    const int kind = closest_hit<cf(COUNT, CF_COUNT) | cf(BVH, CF_BVH) | CF_CUDA, SE>(kp, o, d, t, idx, cnt);
     if (kind == HIT_NONE) return false;
     hp = o + muls(d, t);                                 // ray_at
     if (kind == HIT_SPHERE) {
@@ -369,14 +369,14 @@ struct LanePath {
     // the whole cast in one go (spheres, then brute-force triangles)
     __device__ __forceinline__ void cast_flat(const KParams& kp, Cnt& cnt)
     {
-        kind = closest_hit<COUNT, false>(kp, o, cd, best, win, cnt);
+        kind = closest_hit<cf(COUNT, CF_COUNT)>(kp, o, cd, best, win, cnt);
         state = SM_RESOLVE;
     }
 
     // closest_hit's sphere half and the traversal set-up
     __device__ __forceinline__ void cast(const KParams& kp, Cnt& cnt)
     {
-        win = cast_spheres<COUNT, false>(kp, o, cd, best, cnt);
+        win = cast_spheres<cf(COUNT, CF_COUNT)>(kp, o, cd, best, cnt);
         kind = win >= 0 ? HIT_SPHERE : HIT_NONE;
         win_orig = 0;
         if (kp.bvh) r32 = ray32(kp, o, cd);

@@ -8,7 +8,9 @@
 // Semantics follow main.c (the authoritative CPU path), not main_cuda.cu
 // (reference lines -> function, file; this file includes the headers in
 // definition order and keeps the small kernels and the launchers, which execute
-// the host's plan, rt_launch_plan.cpp plan_render):
+// the host's plan, rt_launch_plan.cpp plan_render; the queue kernel's (QB, OPQ)
+// instantiations are rt_queue_variants.h's table, shared with that plan, and
+// rt_queue.h QVariant holds what the device derives from a row):
 //   fill_canva        main.c:245-284      -> render_kernel_q (task queue; decode_task is its one
 //                                            task decoder), rt_queue.h / render_kernel (fixed
 //                                            grid; tile_row: local tile row -> frame row),
@@ -87,7 +89,7 @@ static_assert(RT_CAND_M * RT_CAND_M * RT_CAND_T1 >= 0x1.8p-89 && RT_CAND_M <= 0x
 #define RT_FWD_CEXP 44
 // Occupancy bounds (waves per SIMD): the fixed-grid kernels, the fixed-grid
 // BVH variant (traversal state + LDS stack), and the queue kernel with its
-// shallow-tree (QB 4) and sphere-only (QB < 0) instantiations.
+// shallow-tree and sphere-only instantiations (rt_queue.h QVariant::WAVES).
 #ifndef RT_WAVES_PER_SIMD
 #define RT_WAVES_PER_SIMD 4
 #endif
@@ -100,7 +102,7 @@ static_assert(RT_CAND_M * RT_CAND_M * RT_CAND_T1 >= 0x1.8p-89 && RT_CAND_M <= 0x
 #ifndef RT_WAVES_PER_SIMD_Q4
 #define RT_WAVES_PER_SIMD_Q4 RT_WAVES_PER_SIMD_Q
 #endif
-#ifndef RT_WAVES_PER_SIMD_QW        // QB 5 (wide trees): 46 KiB of LDS, three blocks per CU
+#ifndef RT_WAVES_PER_SIMD_QW        // QB_WIDE (wide trees): 46 KiB of LDS, three blocks per CU
 #define RT_WAVES_PER_SIMD_QW 3
 #endif
 #ifndef RT_WAVES_PER_SIMD_QS
@@ -113,10 +115,10 @@ static_assert(RT_CAND_M * RT_CAND_M * RT_CAND_T1 >= 0x1.8p-89 && RT_CAND_M <= 0x
 #ifndef RT_WALK_PRIO                // BVH queue kernel: wave priority during its walk steps (0: off).  The walk
 #define RT_WALK_PRIO 2              // is a chain of dependent node/record loads; ahead of the other waves'
 #endif                              // VALU it issues sooner
-#ifndef RT_QB_TOP                   // QB 4: nodes of the tree's top levels copied to LDS (x 128 B; the block
+#ifndef RT_QB_TOP                   // QB_TOP: nodes of the tree's top levels copied to LDS (x 128 B; the block
 #define RT_QB_TOP 40                // then needs <= 40 KiB of LDS, still 4 blocks per CU)
 #endif
-// node visits per round of the deep-tree instantiations (QB 3): RT_QW_MIN,
+// node visits per round of the deep-tree instantiations (QB_DEEP, QB_WIDE): RT_QW_MIN,
 // then more while >= RT_QW_LANES lanes still walk, at most RT_QW_MAX
 #ifndef RT_QW_MIN
 #define RT_QW_MIN 3
@@ -349,13 +351,15 @@ static void launch_variant(const KParams& kp, const RenderPlan& pl, void* stream
     hipLaunchKernelGGL(kernel, grid_for(kp), dim3(256), 0, (hipStream_t)stream, kp);
 }
 
-// The 28 render_kernel_q instantiations, (QB, OPQ) x sky x AO, described once:
-// with_queue_variant maps the plan's tuple to a QVariant and hands it to f, so
-// the kernel pointer and its occupancy cache cannot disagree.
-template <bool SKY, int AOM, int QB, bool OPQ>
-struct QVariant {
-    static constexpr void (*kernel)(const KParams) = render_kernel_q<SKY, AOM, QB, OPQ>;
-};
+// The 28 render_kernel_q instantiations: rt_queue_variants.h's (QB, OPQ) pairs
+// x sky x AO.  with_queue_variant maps the plan's tuple to its QVariant
+// (rt_queue.h) and hands it to f, so the kernel pointer and its occupancy cache
+// cannot disagree; false (f not called) when the pair is not in the list.  (A
+// row's kernels are named before the next row is looked at: the code object
+// holds the kernels in the table's order.)
+using QueueKernel = void (*)(const KParams);
+template <class V>
+constexpr QueueKernel queue_kernel(V) { return render_kernel_q<V::SKY, V::AOM, V::QB, V::OPQ>; }
 template <int QB, bool OPQ, class F>
 static void with_queue_variant_qb(const RenderPlan& pl, F&& f)
 {
@@ -364,16 +368,19 @@ static void with_queue_variant_qb(const RenderPlan& pl, F&& f)
     else if (pl.ao) f(QVariant<false, AO_ON, QB, OPQ>{});
     else f(QVariant<false, AO_OFF, QB, OPQ>{});
 }
-template <class F>
-static void with_queue_variant(const RenderPlan& pl, F&& f)
+template <int I = 0, class F>
+static bool with_queue_variant(const RenderPlan& pl, F&& f)
 {
-    if (pl.qb == 3 && pl.opq) with_queue_variant_qb<3, true>(pl, f);
-    else if (pl.qb == 3) with_queue_variant_qb<3, false>(pl, f);
-    else if (pl.qb == 4) with_queue_variant_qb<4, false>(pl, f);
-    else if (pl.qb == 5) with_queue_variant_qb<5, false>(pl, f);
-    else if (pl.qb == -2) with_queue_variant_qb<-2, false>(pl, f);
-    else if (pl.qb == -1) with_queue_variant_qb<-1, false>(pl, f);
-    else with_queue_variant_qb<0, false>(pl, f);
+    if constexpr (I < kQueueVariantCount) {
+        constexpr QueueVariant v = kQueueVariants[I];
+        if (pl.qb == v.qb && pl.opq == v.opq) {
+            with_queue_variant_qb<v.qb, v.opq>(pl, f);
+            return true;
+        }
+        return with_queue_variant<I + 1>(pl, f);
+    } else {
+        return false;
+    }
 }
 
 // Resident blocks of the queue kernel on this device (grid of render_kernel_q).
@@ -390,7 +397,7 @@ static unsigned queue_grid(V)
     int c = slot.load(std::memory_order_relaxed);
     if (c <= 0) {
         int nb = 0, ncu = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, V::kernel, 256, 0);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, queue_kernel(V{}), 256, 0);
         (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
         c = std::max(1, nb) * std::max(1, ncu);
         if (std::getenv("RT_QUEUE_VERBOSE")) std::fprintf(stderr, "render_kernel_q: %d blocks/CU x %d CUs -> %d\n", nb, ncu, c);
@@ -414,13 +421,14 @@ int launch_render(const KParams& kp, const RenderPlan& pl, void* stream)
     t_last_kernel = pl.name;
     if (pl.queue) {
         const hipStream_t st = (hipStream_t)stream;
-        (void)hipMemsetAsync(kp.task_ctr, 0, sizeof(unsigned), st);
-        void (*kernel)(const KParams) = nullptr;
+        QueueKernel kernel = nullptr;
         unsigned nb = 0;
-        with_queue_variant(pl, [&](auto v) {
-            kernel = v.kernel;
+        const bool listed = with_queue_variant(pl, [&](auto v) {
+            kernel = queue_kernel(v);
             nb = queue_grid(v);
         });
+        if (!listed) return (int)hipErrorInvalidValue;       // a (qb, opq) that plan_render cannot give
+        (void)hipMemsetAsync(kp.task_ctr, 0, sizeof(unsigned), st);
         unsigned long long* tr = nullptr;
         const char* tf = std::getenv("RT_QUEUE_TRACE");
         if (tf) (void)hipMalloc((void**)&tr, (size_t)nb * 256 * RT_TRACE_WORDS * sizeof(unsigned long long));

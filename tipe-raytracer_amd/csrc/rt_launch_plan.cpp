@@ -132,21 +132,21 @@ void set_tiling(KParams& kp, const rt_tiling* t, int H)
 //    render band's chunks * pixels below 2^31), RT_SEM_MAIN_C, no running sums
 //    and, with a BVH, a walk that admits the tree; every other launch takes the
 //    fixed grid (kStack4 entries).
+//  * Which queue kernel: one of rt_queue_variants.h's kQueueVariants, which says
+//    what each (QB, OPQ) pair walks, its stack and whether it has the far-origin
+//    margins.  The rules here admit a scene to a pair.
 //  * Which walk, by the tree's exact stack bound (bvh_stack; narrow trees above
-//    kStackQN: none).  QB 4 (128-byte nodes, 4 visits per round, kStackQ4
-//    entries, no far-origin margins) takes shallow trees (bvh_steps 4) and deep
-//    ones that have no 64-byte nodes, when the bound fits and no origin is far.
-//    Everything else is QB 3 over the 64-byte nodes bvhh (kStackQN entries), if
-//    the tree has them; its OPQ form (kStackQ entries) when every material is
-//    opaque, the bound fits and no origin is far.
-//  * A wide tree (indices beyond 16 bits) takes QB 5 over its own 64-byte nodes
-//    bvhw when they packed and the bound is at most kStackQW, else the fixed
-//    grid's wide instantiation; no narrow kernel walks it, and a narrow tree
-//    never takes a wide kernel.
-//  * Without a BVH: QB -2 (sphere-only scene, every material opaque), -1
-//    (sphere-only) or 0 (few triangles).
-// stack_cap is that kernel's stack, which COUNT runs check every push against
-// (RT_CNT_BVH_STACK_OVER).
+//    kStackQN: none).  QB_TOP takes shallow trees (bvh_steps 4) and deep ones
+//    that have no 64-byte nodes, when the bound fits and no origin is far.
+//    Everything else is QB_DEEP, if the tree has its 64-byte nodes bvhh; the OPQ
+//    form when every material is opaque, the bound fits and no origin is far.
+//  * A wide tree (indices beyond 16 bits) takes QB_WIDE when its own 64-byte
+//    nodes bvhw packed and the bound fits, else the fixed grid's wide
+//    instantiation; no narrow kernel walks it, and a narrow tree never takes a
+//    wide kernel.
+//  * Without a BVH: QB_SPH_OPAQUE, QB_SPH or QB_SCAN.
+// stack_cap and name are the pair's table entry (the fixed grid: kStack4); COUNT
+// runs check every push against stack_cap (RT_CNT_BVH_STACK_OVER).
 RenderPlan plan_render(const KParams& kp, bool count)
 {
     RenderPlan pl = {};
@@ -171,29 +171,27 @@ RenderPlan plan_render(const KParams& kp, bool count)
     if (pl.wide) {
         if (can_queue && kp.bvhw != nullptr && kp.bvh_stack <= kStackQW) {
             pl.queue = true;
-            pl.qb = 5;
-            pl.stack_cap = kStackQW;
+            pl.qb = QB_WIDE;
         }
     } else if (!pl.bvh) {
         pl.queue = can_queue;
-        if (pl.queue) pl.qb = kp.nt == 0 ? (kp.opaque ? -2 : -1) : 0;
+        if (pl.queue) pl.qb = kp.nt == 0 ? (kp.opaque ? QB_SPH_OPAQUE : QB_SPH) : QB_SCAN;
     } else if (kp.bvh_stack <= kStackQN) {
         const bool fits4 = kp.bvh_stack <= kStackQ4 && !kp.bvh_far;
-        pl.qb = fits4 && (kp.bvh_steps > 3 || kp.bvhh == nullptr) ? 4 : 3;
-        pl.queue = can_queue && (pl.qb == 4 || kp.bvhh != nullptr);
-        if (pl.queue) {
-            pl.opq = pl.qb == 3 && kp.opaque_all && kp.bvh_stack <= kStackQ && !kp.bvh_far;
-            pl.stack_cap = pl.qb == 4 ? kStackQ4 : pl.opq ? kStackQ : kStackQN;
-        }
+        pl.qb = fits4 && (kp.bvh_steps > 3 || kp.bvhh == nullptr) ? QB_TOP : QB_DEEP;
+        pl.queue = can_queue && (pl.qb == QB_TOP || kp.bvhh != nullptr);
+        if (pl.queue) pl.opq = pl.qb == QB_DEEP && kp.opaque_all && kp.bvh_stack <= kStackQ && !kp.bvh_far;
     }
-    if (!pl.queue) pl.qb = 0;
-    // tests and bench.py read these (rt_last_render_kernel)
-    static const char* const by_qb[] = {"render_kernel_q<QB=-2>", "render_kernel_q<QB=-1>", "render_kernel_q<QB=0>", "", "",
-                                        "render_kernel_q<QB=3>",  "render_kernel_q<QB=4>",  "render_kernel_q<QB=5>"};
-    pl.name = pl.queue  ? (pl.opq ? "render_kernel_q<QB=3,OP>" : by_qb[pl.qb + 2])
-              : pl.cuda ? "render_kernel_cuda"
-              : pl.bvh  ? (pl.wide ? "render_kernel<BVH32>" : "render_kernel<BVH>")
-                        : "render_kernel";
+    if (pl.queue) {
+        const QueueVariant& v = queue_variant(pl.qb, pl.opq);       // (the rules above pick listed pairs)
+        pl.stack_cap = v.stack;
+        pl.name = v.name;
+    } else {
+        pl.qb = 0;
+        pl.name = pl.cuda  ? "render_kernel_cuda"
+                  : pl.bvh ? (pl.wide ? "render_kernel<BVH32>" : "render_kernel<BVH>")
+                           : "render_kernel";
+    }
     return pl;
 }
 

@@ -7,6 +7,7 @@
 #pragma once
 #include <cstring>
 
+#include "rt_queue_variants.h"
 #include "rt_scene_prep.h"
 
 namespace rt {
@@ -91,7 +92,8 @@ struct RenderPlan {
     int band_rows;           // local rows per launch; the partials are per band (a count run: one band)
     size_t partial_bytes;    // chunk partials of one band, [chunks][band_rows*W][9] doubles (0: none)
     bool task_ok;            // spp_chunks > 1 and the render's tasks per band fit the queue's 32-bit numbering
-    bool queue;              // the render is render_kernel_q<qb, opq, sky, ao>, else the fixed grid's
+    bool queue;              // the render is render_kernel_q<qb, opq, sky, ao> -- (qb, opq) one of
+                             // rt_queue_variants.h kQueueVariants --, else the fixed grid's
     int qb;
     bool opq, sky, ao;
     bool cuda, bvh, wide;    // the fixed-grid instantiation (with sky); a count run always takes it

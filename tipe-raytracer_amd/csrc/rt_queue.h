@@ -65,22 +65,79 @@ struct QHit {
                                      // re-reads the material from it instead of redoing the barycentrics
 };
 
-// NT: the scene has no triangles (every hit is a sphere); OP: every material
-// is opaque (host: !(alpha < 0.0001) && !(alpha <= 0.99), so no alpha hole
-// and no refraction branch is ever taken and neither is compiled in)
-// IR: incomingLight / rayColor live in the lane's LDS column (slots
-// ACC_SLOTS..+5 of the sums array) instead of twelve VGPRs
-// KT: a refraction lane keeps its triangle hit's texel (QHit::tex) from
-// resolve_hit to finish_bounce instead of redoing the barycentrics (the
-// brute-force kernel, QB 0: C3 +7.0 %, C5 +6.7 %; the BVH kernels recompute,
-// their registers are tighter: sweep -1.9 % with KT)
-// PD: paired draws (render_kernel_q's step 4): OP without AO; then resolve_hit
-// moves o to the hit point of every hit (a lit lane's path is over, its o is
-// dead) and skips the miss's identity adds
-template <bool SKY, int AOM, bool NT = false, bool OP = false, int IR = 0, bool KT = false,   // IR 1: incomingLight only
-          bool PD = false>
-struct QPath {
+// One render_kernel_q instantiation: its row T of rt_queue_variants.h's table
+// (what the (QB, OPQ) pair means, shared with the host) and, derived from it
+// once, what only the device build knows (the RT_* tunables of rt_kernels.hip,
+// AO_ON).  QPath and render_kernel_q read these; nothing else compares QB.
+template <bool SKY_, int AOM_, int QB_, bool OPQ_>   // OPQ: (BVH scenes) every material opaque
+struct QVariant {
+    static_assert(queue_variant_index(QB_, OPQ_) >= 0, "not a pair of kQueueVariants (e.g. the wide-tree kernel has no "
+                                                       "opaque specialisation)");
+    static constexpr QueueVariant T = queue_variant(QB_, OPQ_);
+    static constexpr bool SKY = SKY_, OPQ = OPQ_;
+    static constexpr int AOM = AOM_, QB = QB_;
+    // NT: the scene has no triangles (every hit is a sphere); OP: every material
+    // is opaque (host: !(alpha < 0.0001) && !(alpha <= 0.99), so no alpha hole
+    // and no refraction branch is ever taken and neither is compiled in)
+    static constexpr bool NT = !T.triangles, OP = T.opaque;
+    static constexpr bool BVH = T.nodes != QN_NONE;      // spheres, then a bounded BVH walk per round
+    static constexpr bool DEEP = T.nodes == QN_H || T.nodes == QN_W;   // the deep-tree walk (64-byte nodes in HBM)
+    // Occupancy bound (rt_kernels.hip RT_WAVES_PER_SIMD_*): the sphere-only, the
+    // shallow-tree and the wide-tree kernels have their own (the last: 46 KiB of
+    // LDS, three blocks per CU)
+    static constexpr int WAVES = NT                  ? RT_WAVES_PER_SIMD_QS
+                                 : T.nodes == QN_128 ? RT_WAVES_PER_SIMD_Q4
+                                 : T.nodes == QN_W   ? RT_WAVES_PER_SIMD_QW
+                                                     : RT_WAVES_PER_SIMD_Q;
+    // IR: incomingLight / rayColor live in the lane's LDS column (slots
+    // ACC_SLOTS..+5 of the sums array) instead of twelve VGPRs: both (2) for the
+    // non-BVH kernels, incomingLight alone (1) for the opaque deep-tree kernel
+    // (its stack leaves room for 3 doubles)
+    static constexpr int IR = !BVH ? 2 : OP ? 1 : 0;
+    // KT: a refraction lane keeps its triangle hit's texel (QHit::tex) from
+    // resolve_hit to finish_bounce instead of redoing the barycentrics (the
+    // brute-force kernel, QB_SCAN: C3 +7.0 %, C5 +6.7 %; the BVH kernels recompute,
+    // their registers are tighter: sweep -1.9 % with KT)
+    static constexpr bool KT = T.triangles && !BVH;
+    // PD: paired draws (render_kernel_q's step 4).  Every material opaque and no
+    // AO, so a sample's draws are fixed -- the camera takes draws 0-3 (Philox
+    // block 0) and bounce i draws 4 + 2i and 5 + 2i: a bounce with even i opens
+    // block 1 + i/2, uses its words 0, 1 and keeps words 2, 3 (kw2, kw3) for
+    // bounce i + 1.  Step 4 then needs neither the draw count st.n nor the block
+    // cache in LDS; resolve_hit moves o to the hit point of every hit (a lit
+    // lane's path is over, its o is dead) and skips the miss's identity adds.  The
+    // sphere-only kernels take this form; the opaque deep-tree kernel (QB_DEEP,
+    // OPQ) has no registers to spare and keeps the general one.
+    static constexpr bool PD = NT && OP && AOM != AO_ON;
     static_assert(!PD || (OP && AOM != AO_ON), "paired draws: two draws per bounce, none else");
+    // TTAB: each wave decodes its batches of tasks into LDS -- every
+    // instantiation but the deep-tree ones, where the table's registers cost spills
+    static constexpr bool TTAB = !DEEP;
+    // shallow trees (QB_TOP: depth4 <= 4, e.g. the 50-node sweep tree) keep
+    // their top nodes in LDS, as 128-byte nodes; deep trees walk the 64-byte
+    // nodes in HBM (HN, bvh_step's node form; host: kp.bvhh / kp.bvhw set)
+    static constexpr int HN = BVH ? T.nodes : 0;
+    static constexpr int NTOP = T.nodes == QN_128 ? RT_QB_TOP : 0;
+    // Node visits per round.  Deep trees: at least RT_QW_MIN visits, then more
+    // while at least RT_QW_LANES lanes of the wave are still walking, up to
+    // RT_QW_MAX (long walks -- e.g. rays skimming RTX_MAP/nature's terrain --
+    // finish in fewer rounds, short ones hand the wave back to the path work as
+    // before); QB_TOP: its own value
+    static constexpr int JMIN = DEEP ? RT_QW_MIN : BVH ? QB : 0, JMAX = DEEP ? RT_QW_MAX : BVH ? QB : 0;
+    static constexpr bool FAR = T.far;                   // ray32's far-origin margins
+    // The cast (rt_spheres.h CF_*).  Before a BVH walk: the plain candidate loop.
+    // Else the pair loops (closest_hit adds them itself), in the kernels without
+    // AO or sky with the AMGM bound; the paired-draw kernels test in half-b units.
+    static constexpr unsigned CAST = BVH ? CF_NONE
+                                         : cf(!SKY && AOM != AO_ON, CF_AMGM) | cf(NT, CF_PAIRS) | cf(PD, CF_HALFB);
+    static constexpr int PHASE_CAST = BVH ? 1 : 0;       // RT_PHASE_CLOCK: the slot that ends at step 2 (the walk's,
+                                                         // else the cast's)
+};
+
+template <class V>
+struct QPath {
+    static constexpr bool SKY = V::SKY, NT = V::NT, OP = V::OP, KT = V::KT, PD = V::PD;
+    static constexpr int AOM = V::AOM, IR = V::IR;       // IR 1: incomingLight only
     V3 o, d, cd, inc, rc;            // cd: the cast's direction (AO casts; else d)
     double* accp;                    // (IR) the lane's LDS column
     double top_n2, best;
@@ -396,38 +453,26 @@ __device__ __forceinline__ void decode_task(KParamsK K, unsigned t, uint32_t e[k
     e[4] = (uint32_t)chunk_start(K->S, K->chunks, K->chunk_taper, K->chunk_den, K->qm_chunks, chunk + 1u);
 }
 
-// QB 5: a wide tree (rt_bvh.h BvhBuild::wide) -- the non-opaque deep-tree
-// kernel (QB 3, not OPQ: every material branch, the adaptive visit count, the
+// The (QB, OPQ) pairs are rt_queue_variants.h's, the constants QVariant's (V).
+// QB_WIDE: a wide tree (rt_bvh.h BvhBuild::wide) -- the non-opaque deep-tree
+// kernel (QB_DEEP, not OPQ: every material branch, the adaptive visit count, the
 // far-origin margins, the walk priority) over the BvhNodeW nodes kp.bvhw with
-// the 24-bit stack bvh_stack_qw (kStackQW entries); its 46 KiB of LDS allow
-// three blocks per CU, RT_WAVES_PER_SIMD_QW waves per SIMD.
-template <bool SKY, int AOM, int QB, bool OPQ = false>   // OPQ: (BVH scenes) every material opaque
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QB < 0 ? RT_WAVES_PER_SIMD_QS
-                                                                     : QB == 4 ? RT_WAVES_PER_SIMD_Q4
-                                                                     : QB == 5 ? RT_WAVES_PER_SIMD_QW
-                                                                               : RT_WAVES_PER_SIMD_Q)))
+// the 24-bit stack bvh_stack_qw; its 46 KiB of LDS allow three blocks per CU,
+// RT_WAVES_PER_SIMD_QW waves per SIMD.
+template <bool SKY, int AOM, int QB, bool OPQ = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QVariant<SKY, AOM, QB, OPQ>::WAVES)))
 void render_kernel_q(const KParams kp)
 {
-    static_assert(QB != 5 || !OPQ, "the wide-tree kernel has no opaque specialisation");
-    constexpr bool DEEP = QB == 3 || QB == 5;            // the deep-tree walk (64-byte nodes in HBM)
-    // incomingLight / rayColor in LDS: both for the non-BVH kernels, incomingLight
-    // alone for the opaque deep-tree kernel (its stack leaves room for 3 doubles)
-    constexpr int QIR = QB <= 0 ? 2 : (QB == 3 && OPQ) ? 1 : 0;
-    __shared__ double acc_lds[(ACC_SLOTS + 3 * QIR) * 256];
+    using V = QVariant<SKY, AOM, QB, OPQ>;
+    constexpr bool PD = V::PD, TTAB = V::TTAB;
+    constexpr int NTOP = V::NTOP, HN = V::HN;
+    __shared__ double acc_lds[(ACC_SLOTS + 3 * V::IR) * 256];
     __shared__ uint32_t rng_lds[4 * 256];
     double* acc = acc_lds + threadIdx.x;
     uint32_t* rng = rng_lds + threadIdx.x;
     const int lane = threadIdx.x & 63;
     unsigned qb = 0, qe = 0;         // the wave's batch of tasks [qb, qe) (wave-uniform)
-    // Paired draws: every material opaque and no AO, so a sample's draws are
-    // fixed -- the camera takes draws 0-3 (Philox block 0) and bounce i draws
-    // 4 + 2i and 5 + 2i: a bounce with even i opens block 1 + i/2, uses its
-    // words 0, 1 and keeps words 2, 3 (kw2, kw3) for bounce i + 1.  Step 4 then
-    // needs neither the draw count st.n nor the block cache in LDS.  The
-    // sphere-only kernels take this form; the opaque deep-tree kernel (QB 3,
-    // OPQ) has no registers to spare and keeps the general one.
-    constexpr bool PD = QB == -2 && AOM != AO_ON;
-    QPath<SKY, AOM, QB < 0, QB == -2 || OPQ, QIR, QB == 0, PD> L;
+    QPath<V> L;
     L.init(acc);
     uint32_t kw2 = 0, kw3 = 0;       // (PD) the kept words of the sample's current block
     // (PD) A block's counter is {block, 0, pixel, sample} and the pixel is the
@@ -451,17 +496,9 @@ void render_kernel_q(const KParams kp)
     int node = 0, sp = 0, win_orig = 0;      // BVH walk in flight (state SM_TRAV)
     unsigned pixel = 0, qidx = 0;    // the lane's task: its pixel and its chunk-partial index (decode_task e[1], e[0])
     bool owns = false;               // the lane's LDS sums belong to that task
-    // every instantiation but the deep-tree ones (QB 3 and 5, where the table's
-    // registers cost spills): each wave decodes its batches of tasks into LDS
-    constexpr bool TTAB = !DEEP;
     __shared__ uint32_t ttab_lds[TTAB ? 4 * kTaskWords * 64 : 1];
     Stream st;                       // draw stream of the sample in flight (next31 for refraction / AO)
     st.start(0u, 0u, kp.key0, kp.key1, rng);
-    // shallow trees (QB 4: depth4 <= 4, e.g. the 50-node sweep tree) keep
-    // their top nodes in LDS, as 128-byte nodes; deep trees (QB 3) walk the
-    // 64-byte nodes in HBM (HN; host: kp.bvhh set)
-    constexpr int HN = QB == 5 ? 2 : QB == 3 ? 1 : 0;    // bvh_step's node form
-    constexpr int NTOP = QB == 4 ? RT_QB_TOP : 0;
     if (NTOP > 0) {                          // the tree's top nodes into LDS, once per block
         float4* dst = (float4*)bvh_top_q<NTOP>();
         const float4* src = (const float4*)kp.bvh;
@@ -487,14 +524,14 @@ void render_kernel_q(const KParams kp)
         ++rounds;
         RT_PHASE(4);                 // the previous round's next-ray step and finish_bounce
         // ---- 1. closest hit (main.c:52-92) for every lane with a ray ------
-        if (QB > 0) {
-            // spheres, then the triangle BVH: up to QB node visits
+        if constexpr (V::BVH) {
+            // spheres, then the triangle BVH: up to V::JMAX node visits
             // per round; a deeper walk resumes next round (its lane skips
             // the path work meanwhile), so a wave never waits for its
             // deepest lane's whole walk
             if (L.state == SM_CAST) {
                 Cnt cnt;
-                L.win = cast_spheres<false, false>(kp, L.o, L.cast_dir(), L.best, cnt);
+                L.win = cast_spheres<V::CAST>(kp, L.o, L.cast_dir(), L.best, cnt);
                 L.kind = L.win >= 0 ? HIT_SPHERE : HIT_NONE;
                 win_orig = 0;
                 node = 0;
@@ -507,17 +544,11 @@ void render_kernel_q(const KParams kp)
                 __builtin_amdgcn_s_setprio(RT_WALK_PRIO);
 #endif
                 const V3 dd = L.cast_dir();
-                const Ray32 r32 = ray32<DEEP && !OPQ>(kp, L.o, dd);
+                const Ray32 r32 = ray32<V::FAR>(kp, L.o, dd);
                 const auto stk = bvh_stack_for_q<QB, OPQ>();
                 const BvhNode4* top = NTOP > 0 ? bvh_top_q<NTOP>() : nullptr;
-                // deep trees (QB 3): at least RT_QW_MIN visits, then more while at
-                // least RT_QW_LANES lanes of the wave are still walking, up to
-                // RT_QW_MAX (long walks -- e.g. rays skimming RTX_MAP/nature's
-                // terrain -- finish in fewer rounds, short ones hand the wave back
-                // to the path work as before)
-                constexpr int JMIN = DEEP ? RT_QW_MIN : QB, JMAX = DEEP ? RT_QW_MAX : QB;
 #pragma unroll 1
-                for (int j = 0; j < JMAX; ++j) {
+                for (int j = 0; j < V::JMAX; ++j) {
                     if (L.state == SM_TRAV) {
                         Cnt cnt;
                         if (!bvh_step<false, false, NTOP, HN>(kp, L.o, dd, r32, stk, node, sp, L.best, L.kind, L.win,
@@ -525,23 +556,23 @@ void render_kernel_q(const KParams kp)
                             L.state = SM_RESOLVE;
                     }
                     const unsigned long long wm = __ballot(L.state == SM_TRAV);
-                    if (wm == 0ull || (j + 1 >= JMIN && __popcll(wm) < RT_QW_LANES)) break;
+                    if (wm == 0ull || (j + 1 >= V::JMIN && __popcll(wm) < RT_QW_LANES)) break;
                 }
 #if RT_WALK_PRIO
                 __builtin_amdgcn_s_setprio(0);
 #endif
             }
-        } else if (QB < 0 && L.state == SM_CAST) {          // sphere-only scenes: no triangle scan
+        } else if (V::NT && L.state == SM_CAST) {          // sphere-only scenes: no triangle scan
             Cnt cnt;
-            L.win = cast_spheres<false, false, !SKY && AOM != AO_ON, true, PD>(kp, L.o, L.cast_dir(), L.best, cnt);
+            L.win = cast_spheres<V::CAST>(kp, L.o, L.cast_dir(), L.best, cnt);
             L.kind = L.win >= 0 ? HIT_SPHERE : HIT_NONE;
             L.state = SM_RESOLVE;
         } else if (L.state == SM_CAST) {
             Cnt cnt;
-            L.kind = closest_hit<false, false, false, !SKY && AOM != AO_ON>(kp, L.o, L.cast_dir(), L.best, L.win, cnt);
+            L.kind = closest_hit<V::CAST>(kp, L.o, L.cast_dir(), L.best, L.win, cnt);
             L.state = SM_RESOLVE;
         }
-        RT_PHASE(QB > 0 ? 1 : 0);
+        RT_PHASE(V::PHASE_CAST);
         // ---- 2. the hit, up to the next direction --------------------------
         int role = ROLE_NONE;
         QHit H;

@@ -268,7 +268,7 @@ __device__ __forceinline__ double ao_factor(const KParams& kp, const V3 p, const
     const V3 dir = normalize(n + rd);
     double t;
     int idx;
-    const int kind = closest_hit<COUNT, BVH, CU, false, SE>(kp, p, dir, t, idx, cnt);
+    const int kind = closest_hit<cf(COUNT, CF_COUNT) | cf(BVH, CF_BVH) | cf(CU, CF_CUDA), SE>(kp, p, dir, t, idx, cnt);
     return ao_tail(kind != HIT_NONE, p, dir, t, AO);
 }
 

@@ -71,12 +71,28 @@ __device__ __forceinline__ bool disc_positive(const SphGeo& s, const V3 o, const
     return b * b - four_a * c > 0;
 }
 
+// What a cast is compiled for: the one template parameter of cast_spheres,
+// spheres_closest, spheres_exact_scan and closest_hit (rt_triangles.h), or-ed
+// from these bits, so that a call site names what it switches on.  (In
+// brackets: the names the functions give the bits; each explains its own.)
+enum : unsigned {
+    CF_NONE = 0u,         // main.c's thresholds, no counters, the plain candidate loop, no BVH
+    CF_COUNT = 1u << 0,   // [COUNT] the RT_CNT_* counters
+    CF_CUDA = 1u << 1,    // [CU] main_cuda.cu's thresholds
+    CF_AMGM = 1u << 2,    // [AMGM] Hs from sqrt(a) <= (1 + a)/2; takes CF_PAIRS with it
+    CF_PAIRS = 1u << 3,   // [MG] the candidate pass's pair loops
+    CF_HALFB = 1u << 4,   // [HB] the exact tests in half-b units; without CF_COUNT and CF_CUDA
+    CF_BVH = 1u << 5,     // [BVH] closest_hit alone: the triangles by the BVH walk
+};
+constexpr unsigned cf(bool on, unsigned bits) { return on ? bits : CF_NONE; }
+
 // Exact reference scan over every sphere (main.c:59-78 with hit_sphere).
 // HB: sphere_exact_hb, with a in two_a's place and rcp_refined(a) in rc2a's (cast_spheres).
-template <bool CU, bool HB = false>
+template <unsigned F>
 __device__ __forceinline__ int spheres_exact_scan(const KParams& kp, const V3 o, const V3 d, double two_a,
                                                   double four_a, bool fast, double rc2a, double& t_best)
 {
+    constexpr bool CU = (F & CF_CUDA) != 0, HB = (F & CF_HALFB) != 0;
     const cdptr sg = (cdptr)kp.sph;
     double t = dinf();
     int win = -1;
@@ -293,10 +309,12 @@ __device__ __forceinline__ void cand_second_tail(const CandRay& r, double h1, do
 // HB: the winner's test and the rescan in half-b units (sphere_exact_hb): the
 // caller passes a for two_a, rcp_refined(a) for rc2a and halfb_fast_a(a) for
 // fast, whose window implies the one the comments here assume (2a in 2^+-100).
-template <bool COUNT, bool CU, bool AMGM = false, bool MG = AMGM, bool HB = false>
+template <unsigned F>
 __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, const V3 d, double a, double two_a,
                                                double four_a, bool fast, double rc2a, double& t_best, Cnt& cnt)
 {
+    constexpr bool COUNT = (F & CF_COUNT) != 0, CU = (F & CF_CUDA) != 0, AMGM = (F & CF_AMGM) != 0;
+    constexpr bool MG = (F & (CF_PAIRS | CF_AMGM)) != 0, HB = (F & CF_HALFB) != 0;
     static_assert(!HB || (!COUNT && !CU), "half-b units: the reference thresholds, no counters");
     const cdptr sc = (cdptr)kp.sph_cand;
     const double INF = dinf();
@@ -516,7 +534,7 @@ __device__ __forceinline__ int spheres_closest(const KParams& kp, const V3 o, co
     }
     if (amb) {               // exact reference scan for this ray
         if (COUNT) cnt.c[RT_CNT_EXACT_RESCANS] += 1;
-        win = spheres_exact_scan<CU, HB>(kp, o, d, two_a, four_a, fast, rc2a, t);
+        win = spheres_exact_scan<F>(kp, o, d, two_a, four_a, fast, rc2a, t);
     }
     t_best = t;
     return win;

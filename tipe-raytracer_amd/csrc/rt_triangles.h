@@ -118,17 +118,19 @@ __device__ __forceinline__ unsigned short* bvh_stack()
     __shared__ unsigned short stk_lds[kStack4 * 256];
     return stk_lds + threadIdx.x;
 }
-// The queue kernel's per-lane stack (BVH scenes): uint16 [entries][256].  The
-// deep-tree instantiations (QB = 3) get kStackQ = 24 entries (12 KiB) when every
-// material is opaque (OPQ: incomingLight also lives in LDS) and kStackQN = 32
-// (16 KiB) otherwise, which keeps both at <= 40 KiB, i.e. 4 blocks (16 waves) per
-// CU.  The QB = 4 instantiation has kStackQ4 = 14 entries, so its top-node cache
-// and the task table fit the same 40 KiB.  (The capacities are in rt_bvh.h; who
-// is admitted where is plan_render's rule, rt_launch_plan.cpp.)
+// The queue kernel's per-lane stack (BVH scenes): uint16 [entries][256], entries
+// from the pair's row of rt_queue_variants.h -- the number plan_render gives the
+// host as stack_cap.  Why these capacities (rt_bvh.h): QB_DEEP gets kStackQ = 24
+// entries (12 KiB) when every material is opaque (OPQ: incomingLight also lives
+// in LDS) and kStackQN = 32 (16 KiB) otherwise, which keeps both at <= 40 KiB,
+// i.e. 4 blocks (16 waves) per CU.  QB_TOP has kStackQ4 = 14 entries, so its
+// top-node cache and the task table fit the same 40 KiB.
 template <int QB, bool OPQ>
 __device__ __forceinline__ unsigned short* bvh_stack_q()
 {
-    __shared__ unsigned short stkq_lds[(QB == 4 ? kStackQ4 : OPQ ? kStackQ : kStackQN) * 256];
+    constexpr int entries = queue_variant(QB, OPQ).stack;
+    static_assert(entries > 0 && !queue_variant(QB, OPQ).stack24, "a BVH kernel with uint16 stack entries");
+    __shared__ unsigned short stkq_lds[entries * 256];
     return stkq_lds + threadIdx.x;
 }
 // Stack access by element type: a column of uint16 (narrow trees) or uint32
@@ -150,7 +152,8 @@ __device__ __forceinline__ SE* bvh_stack_of()
     if constexpr (sizeof(SE) == 4) return bvh_stack32();
     else return bvh_stack();
 }
-// ... in the queue kernel (QB 5): kStackQW = 32 entries of 24 bits, split into a
+// ... in the queue kernel (QB_WIDE, the one stack24 row of rt_queue_variants.h):
+// kStackQW = 32 entries of 24 bits, split into a
 // uint16 column and a uint8 column, 24 KiB: with the 22 KiB of sums and draws
 // 46 KiB per block, three blocks (12 waves) per CU.  (32 uint32 entries would
 // make it 54 KiB: two blocks.)
@@ -160,8 +163,9 @@ struct Stack24 {
 };
 __device__ __forceinline__ Stack24 bvh_stack_qw()
 {
-    __shared__ unsigned short stkw_lo_lds[kStackQW * 256];
-    __shared__ unsigned char stkw_hi_lds[kStackQW * 256];
+    constexpr int entries = queue_variant(QB_WIDE, false).stack;
+    __shared__ unsigned short stkw_lo_lds[entries * 256];
+    __shared__ unsigned char stkw_hi_lds[entries * 256];
     return Stack24{stkw_lo_lds + threadIdx.x, stkw_hi_lds + threadIdx.x};
 }
 __device__ __forceinline__ void stk_put(Stack24 stk, int sp, int v)
@@ -173,14 +177,14 @@ __device__ __forceinline__ int stk_get(Stack24 stk, int sp)
 {
     return (int)((unsigned)stk.lo[sp * 256] | ((unsigned)stk.hi[sp * 256] << 16));
 }
-// the stack of a queue-kernel instantiation
+// the stack of a queue-kernel instantiation: size and kind from its table row
 template <int QB, bool OPQ>
 __device__ __forceinline__ auto bvh_stack_for_q()
 {
-    if constexpr (QB == 5) return bvh_stack_qw();
+    if constexpr (queue_variant(QB, OPQ).stack24) return bvh_stack_qw();      // (QB_WIDE is the one such row)
     else return bvh_stack_q<QB, OPQ>();
 }
-// ... and the QB 4 block's copy of the tree's top nodes (RT_QB_TOP x 128 B)
+// ... and the QB_TOP block's copy of the tree's top nodes (RT_QB_TOP x 128 B)
 template <int N>
 __device__ __forceinline__ BvhNode4* bvh_top_q()
 {
@@ -545,9 +549,10 @@ __device__ __forceinline__ bool cuda_bbox(const KParams& kp, const V3 o, const V
 // or -1, its t in best (+inf when none).
 // HB: the exact tests in half-b units (rt_shared_math.h sphere_halfb), which read a where the
 // reference form reads 2a and 4a
-template <bool COUNT, bool CU, bool AMGM = false, bool MG = AMGM, bool HB = false>
+template <unsigned F>
 __device__ __forceinline__ int cast_spheres(const KParams& kp, const V3 o, const V3 d, double& best, Cnt& cnt)
 {
+    constexpr bool COUNT = (F & CF_COUNT) != 0, HB = (F & CF_HALFB) != 0;
     const double a = dot(d, d);          // sphere.h:20 (same for every sphere)
     const double two_a = HB ? a : 2 * a; // sphere.h:27,36
     const double four_a = 4 * a;         // sphere.h:24
@@ -559,18 +564,19 @@ __device__ __forceinline__ int cast_spheres(const KParams& kp, const V3 o, const
         cnt.c[RT_CNT_TRI_TESTS] += (unsigned long long)kp.nt;
         wave_slots(cnt, RT_CNT_CAST_LANE_SLOTS);
     }
-    int win = spheres_closest<COUNT, CU, AMGM, MG, HB>(kp, o, d, a, two_a, four_a, fast, rc2a, best, cnt);
+    int win = spheres_closest<F>(kp, o, d, a, two_a, four_a, fast, rc2a, best, cnt);
     return win;
 }
 
-// SE: the BVH stack's element type (uint32_t for a wide tree, rt_bvh.h)
-template <bool COUNT, bool BVH, bool CU = false, bool AMGM = false, class SE = unsigned short>
+// F: CF_COUNT, CF_CUDA, CF_AMGM, CF_BVH; SE: the BVH stack's element type (uint32_t for a wide tree, rt_bvh.h)
+template <unsigned F, class SE = unsigned short>
 __device__ __forceinline__ int closest_hit(const KParams& kp, const V3 o, const V3 d, double& t_best, int& idx,
                                            Cnt& cnt)
 {
+    constexpr bool COUNT = (F & CF_COUNT) != 0, BVH = (F & CF_BVH) != 0, CU = (F & CF_CUDA) != 0;
     double best;
     // the flagged-pair loop (spheres_closest MG) wherever no BVH walk follows
-    int win = cast_spheres<COUNT, CU, AMGM, AMGM || !BVH>(kp, o, d, best, cnt);
+    int win = cast_spheres<(F & ~CF_BVH) | cf(!BVH, CF_PAIRS)>(kp, o, d, best, cnt);
     int kind = win >= 0 ? HIT_SPHERE : HIT_NONE;
     int win_orig = 0;
     if (CU && kp.nt > 0 && !cuda_bbox(kp, o, d)) {

@@ -45,8 +45,8 @@ __global__ __launch_bounds__(256) void verify_spheres_kernel(const KParams kp, c
         Cnt cnt;
         cnt.c[RT_CNT_EXACT_RESCANS] = 0;
         double t1, t2;
-        const int w1 = spheres_closest<true, false, false, true>(kp, o, d, a, two_a, four_a, fast, rc2a, t1, cnt);
-        const int w2 = spheres_exact_scan<false>(kp, o, d, two_a, four_a, fast, rc2a, t2);
+        const int w1 = spheres_closest<CF_COUNT | CF_PAIRS>(kp, o, d, a, two_a, four_a, fast, rc2a, t1, cnt);
+        const int w2 = spheres_exact_scan<CF_NONE>(kp, o, d, two_a, four_a, fast, rc2a, t2);
         fb = cnt.c[RT_CNT_EXACT_RESCANS] != 0;
         bad = w1 != w2 || (w1 >= 0 && __double_as_longlong(t1) != __double_as_longlong(t2));
     }

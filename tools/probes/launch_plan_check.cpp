@@ -10,8 +10,11 @@
 //   facts KEY VALUE ... end
 // gives the scalars the plan depends on with no scene: ns nt bvh_nodes bvh_depth
 // bvh_stack4 bvh_wide r_scene sph_bound sph_opaque tri_opaque, and bvh bvhh bvhw
-// sky (1: the array exists).  Used by tests/test_launch_plan.py.
+// sky (1: the array exists).  With the argument "variants" it reads nothing and
+// prints the queue kernel's table (rt_queue_variants.h) as one JSON line
+// {"variants": [{"qb", "opq", "name", "stack"}, ...]}.  Used by tests/test_launch_plan.py.
 #include <cmath>
+#include <cstring>
 #include "rt_launch_plan.h"
 #include "scene_text.h"
 using namespace rt;
@@ -109,8 +112,23 @@ static void put_plans(const HostScene& hs)
     }
 }
 
-int main()
+static void put_variants()
 {
+    std::printf("{\"variants\": [");
+    for (int i = 0; i < kQueueVariantCount; ++i) {
+        const QueueVariant& v = kQueueVariants[i];
+        std::printf("%s{\"qb\": %d, \"opq\": %d, \"name\": \"%s\", \"stack\": %d}", i ? ", " : "", v.qb, v.opq, v.name,
+                    v.stack);
+    }
+    std::printf("]}\n");
+}
+
+int main(int argc, char** argv)
+{
+    if (argc > 1 && !std::strcmp(argv[1], "variants")) {
+        put_variants();
+        return 0;
+    }
     read_tokens();
     HostScene hs;
     std::string what = next();
