@@ -42,6 +42,10 @@ extern "C" {
  *    rt_denoise_atrous, rt_set_denoise_params): an edge-avoiding a-trous
  *    filter of this library's own -- not OIDN -- that fits the denoise hook.
  *    No existing struct or entry point changed.
+ *    Added to 5 without a new number (nothing existing changed; a caller
+ *    detects them by symbol): the variance-guided denoiser over two
+ *    half-sample accumulators (rt_vdenoise_params, rt_vdenoise_params_init,
+ *    rt_vdenoise_workspace_bytes, rt_vdenoise_async, rt_render_vdenoised).
  * A caller compares rt_abi_version() with the RT_ABI_VERSION it was built
  * against before passing rt_params or counter arrays.                   */
 #define RT_ABI_VERSION 5
@@ -511,6 +515,94 @@ void rt_denoise_atrous(int largeur_image, int hauteur_image, rt_color* canva, rt
 /* The parameters rt_denoise_atrous uses (validated as above; NULL restores
  * the defaults).  Process-wide. */
 int rt_set_denoise_params(const rt_denoise_params* params);
+
+/* ---- variance-guided denoiser over two half-sample accumulators ----------- */
+/* A second denoiser of this library's own, for the pre-gamma radiance: an
+ * edge-avoiding a-trous filter whose colour weight follows a per-pixel
+ * variance estimate, so it smooths a noisy frame hard and leaves a converged
+ * one alone.  The estimate is the dual-buffer one: two accumulators of
+ * rt_accumulate_async over disjoint halves of a pixel's samples are two
+ * independent estimates of the pixel, and the square of half their difference
+ * estimates the variance of their mean.  Like the filter above it is NOT OIDN,
+ * and it is specified here operation by operation: every step is IEEE
+ * binary32 with only + - * / and no contraction, except where "double" is
+ * written, so a float32 restatement of this text equals the GPU bit for bit.
+ *
+ * Inputs: A and B, two accumulators of rt_accumulate_async over the full
+ * frame (W*H*9 doubles each: the radiance, albedo and normal sums of pixel
+ * j*W+i), each holding n = spp_half >= 1 samples per pixel.
+ *
+ * Means and variance, per pixel and channel (rad, alb, nrm: the three sums):
+ *   rap = 1.0 / n                                   (double)
+ *   mX  = (float)(rap * X)  for each of the 9 sums X of A and of B
+ *   c  = 0.5f * (mA_rad + mB_rad)      a = 0.5f * (mA_alb + mB_alb)
+ *   nn = 0.5f * (mA_nrm + mB_nrm)      d = 0.5f * (mA_rad - mB_rad)
+ *   v  = (0.25f*(d0*d0) + 0.5f*(d1*d1)) + 0.25f*(d2*d2)
+ * (v: the variance of the mean under the luminance weights 1/4, 1/2, 1/4,
+ * which are exact in binary).
+ *
+ * Pass i = 0 .. iterations-1, with step s = 2^i, every pixel p:
+ *   - blurred variance: over the 3x3 neighbours q = p + (dx, dy) at step 1
+ *     that lie in the image, dy = -1..1 (outer), dx = -1..1 (inner),
+ *     g = {1/4, 1/2, 1/4}:  gg = g[dy]*g[dx];  bn += gg * v[q];  bd += gg,
+ *     both from +0.0f;  vb = bn / bd;
+ *     L = sl2 * vb + 0x1p-26f,  sl2 = sigma_luminance * sigma_luminance;
+ *   - taps q = p + s*(dx, dy), dy = -2..2 (outer), dx = -2..2 (inner), a tap
+ *     outside the image is skipped:
+ *       D   = c[q] - c[p];  dl = (0.25f*(D0*D0) + 0.5f*(D1*D1)) + 0.25f*(D2*D2)
+ *       dn  = d2(nn), da = d2(a)   (d2 as above: (D0*D0 + D1*D1) + D2*D2)
+ *       num = ((h[dy]*h[dx]) * L) * (sn2*sa2)
+ *       den = ((L + dl) * (sn2 + dn)) * (sa2 + da)
+ *       w   = num / den            (the one true division of a tap)
+ *       acc_ch += w * c[q]_ch;  accv += (w*w) * v[q];  ws += w
+ *     with h the five-tap kernel above, sn2 = sigma_normal*sigma_normal,
+ *     sa2 = sigma_albedo*sigma_albedo, and acc, accv, ws from +0.0f in tap
+ *     order;
+ *   - c'[p] = acc / ws;  v'[p] = accv / (ws*ws).
+ * Colour and variance ping-pong between two buffers (the blur of pass i reads
+ * the variance pass i-1 wrote); a and nn are never filtered.
+ *
+ * Finish: canva = write_color_canva((double)c, 1) (rtutility.h:56-71, the
+ * operations of every render's canva): r = sqrtf(c), then
+ * (int)(256 * clamp((double)r, 0, 0.999)) stored as double.  albedo and
+ * normal, when their pointers are given, receive (A + B) * (1.0 / (2n)) in
+ * double (1.0 / (2n) first); radiance, when given, receives (double)c.
+ * With iterations = 0 the unfiltered mean c is resolved.
+ *
+ * Device data is not validated: non-finite or huge sums give whatever these
+ * operations give.  Out of scope: the rt_denoise_fn hook cannot carry the
+ * radiance or two buffers, so it keeps the a-trous filter above; a rank's
+ * cyclic-tile local frame and multi-device rendering are not covered (the
+ * inputs are assembled frames); there is no albedo demodulation. */
+typedef struct rt_vdenoise_params {
+    int iterations;                              /* 0..8 */
+    float sigma_luminance, sigma_normal, sigma_albedo;   /* each finite and within [2^-8, 2^8] */
+} rt_vdenoise_params;
+/* Defaults: iterations 4; sigmas 4.0f, 0.5f, 0.25f. */
+void rt_vdenoise_params_init(rt_vdenoise_params* p);
+/* Bytes of device scratch rt_vdenoise_async needs for a W x H frame (0 for
+ * W or H below 1 or a frame above 2^30 pixels); its layout is private. */
+size_t rt_vdenoise_workspace_bytes(int W, int H);
+/* Filters the two device accumulators into the planes of `out` on
+ * `hip_stream` (the current device): out->canva is required, out->albedo,
+ * out->normal and out->radiance may be NULL; the accumulators are read-only.
+ * workspace: workspace_bytes >= rt_vdenoise_workspace_bytes(W, H) bytes of
+ * device memory, 16-byte aligned.  Allocates and synchronises nothing.
+ * RT_EINVAL before any device work for W or H < 1 or a frame above 2^30
+ * pixels, a NULL d_sums_a, d_sums_b, params, workspace, out or out->canva,
+ * spp_half < 1, a workspace too small or misaligned, iterations outside 0..8,
+ * a sigma that is not finite or outside [2^-8, 2^8]. */
+int rt_vdenoise_async(int W, int H, const double* d_sums_a, const double* d_sums_b, int spp_half,
+                      const rt_vdenoise_params* params, void* workspace, size_t workspace_bytes,
+                      const rt_frame* out, void* hip_stream);
+/* Renders the whole frame on rt_init's first device and filters it: cached
+ * scene, pooled stream and pinned staging of the drop-ins; two
+ * rt_accumulate_async calls of S/2 samples each at sample offsets 0 and S/2
+ * (S = params->nbRayonParPixel, which must be even and >= 2, else RT_EINVAL),
+ * then rt_vdenoise_async with spp_half = S/2.  canva, and albedo / normal
+ * when not NULL, are written only on success (W*H colours each). */
+int rt_render_vdenoised(const rt_scene* scene, const rt_params* params, const rt_vdenoise_params* vparams,
+                        rt_color* canva, rt_color* albedo, rt_color* normal);
 
 /* Device-math self test: evaluates one device primitive on n host inputs
  * (synchronous, device 0).  op: 0 acos, 1 sinf, 2 cosf, 3 pow(x, y),

@@ -10,32 +10,15 @@
 // albedo | normal.
 #include <hip/hip_runtime.h>
 
+#include "rt_denoise_tile.h"
 #include "rt_internal.h"
 
 namespace rt {
 
 namespace {
 
-struct F3 { float x, y, z; };
-
-__device__ __forceinline__ F3 ld3(const float* __restrict__ p, long long px)
-{
-    const float* q = p + px * 3;
-    return F3{q[0], q[1], q[2]};
-}
-
-// d2(X) = (d0*d0 + d1*d1) + d2*d2, d = X[q] - X[p]
-__device__ __forceinline__ float dist2(const F3 q, const F3 p)
-{
-    const float d0 = q.x - p.x, d1 = q.y - p.y, d2 = q.z - p.z;
-    return (d0 * d0 + d1 * d1) + d2 * d2;
-}
-
 // k(x) = 1 / (1 + x)
 __device__ __forceinline__ float kern(const float x) { return 1.0f / (1.0f + x); }
-
-constexpr int kTileX = 64;          // pixels of one row a wave filters: every tap row is one coalesced run
-constexpr int kTileY = 4;           // rows (waves) per block
 
 // planes -> the workspace's float3 planes (the pack's operations)
 __global__ __launch_bounds__(256) void denoise_prepare_kernel(long long n, const double* __restrict__ canva,
@@ -121,7 +104,6 @@ __global__ __launch_bounds__(kTileX* kTileY) void denoise_pass_kernel(int W, int
 // kTiledMaxStep = 0 selects the plain form everywhere (the A/B of that
 // measurement).  Step 16 uses 36 KiB of LDS with both guide planes.
 constexpr int kTiledMaxStep = 16;
-constexpr int kTiledRows = kTileY + 4;
 inline size_t tiled_lds_bytes(int step, int planes) { return (size_t)planes * 3 * kTiledRows * (kTileX + 4 * step) * sizeof(float); }
 
 template <bool ALB, bool NRM>

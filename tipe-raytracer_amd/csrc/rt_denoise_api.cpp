@@ -2,7 +2,9 @@
 // rt_render_rows calls on a finished frame, the reference's pack/unpack, and
 // the built-in edge-avoiding a-trous filter (rt_denoise.hip) on a device
 // frame (rt_denoise_async), on host arrays (rt_denoise_host) and as a hook
-// (rt_denoise_atrous).
+// (rt_denoise_atrous); and the variance-guided denoiser (rt_vdenoise.hip) on
+// two device accumulators (rt_vdenoise_async) and as a whole-frame render
+// into host arrays (rt_render_vdenoised).
 #include <atomic>
 #include <cmath>
 #include <cstring>
@@ -20,22 +22,48 @@ std::atomic<rt_denoise_fn> g_denoise{nullptr};
 std::mutex g_denoise_mu;
 rt_denoise_params g_denoise_params = kDefaults;    // rt_denoise_atrous's
 
-// frame size and parameters of the built-in denoiser
-int validate_denoise(int W, int H, const rt_denoise_params* p)
+// what the two denoisers validate alike: the frame size, then the pass count and the three sigmas
+int validate_frame_size(int W, int H)
 {
     if (W < 1 || H < 1) return fail(RT_EINVAL, "denoise: frame %dx%d", W, H);
     if ((long long)W * H > (1ll << 30)) return fail(RT_EINVAL, "denoise: frame %dx%d above 2^30 pixels", W, H);
-    if (!p) return fail(RT_EINVAL, "denoise: params is NULL");
-    if (p->iterations < 1 || p->iterations > 8)
-        return fail(RT_EINVAL, "denoise: iterations %d outside 1..8", p->iterations);
-    const float sig[3] = {p->sigma_color, p->sigma_normal, p->sigma_albedo};
-    const char* const name[3] = {"sigma_color", "sigma_normal", "sigma_albedo"};
+    return RT_OK;
+}
+
+int validate_passes(int iterations, int min_iterations, const float* sig, const char* const* name)
+{
+    if (iterations < min_iterations || iterations > 8)
+        return fail(RT_EINVAL, "denoise: iterations %d outside %d..8", iterations, min_iterations);
     for (int i = 0; i < 3; ++i) {
         if (!std::isfinite(sig[i])) return fail(RT_EINVAL, "denoise: %s is not finite", name[i]);
         if (sig[i] < 0x1p-8f || sig[i] > 0x1p8f)
             return fail(RT_EINVAL, "denoise: %s %g outside [2^-8, 2^8]", name[i], (double)sig[i]);
     }
     return RT_OK;
+}
+
+// frame size and parameters of the built-in denoiser
+int validate_denoise(int W, int H, const rt_denoise_params* p)
+{
+    const int rc = validate_frame_size(W, H);
+    if (rc) return rc;
+    if (!p) return fail(RT_EINVAL, "denoise: params is NULL");
+    const float sig[3] = {p->sigma_color, p->sigma_normal, p->sigma_albedo};
+    const char* const name[3] = {"sigma_color", "sigma_normal", "sigma_albedo"};
+    return validate_passes(p->iterations, 1, sig, name);
+}
+
+// ... and of the variance-guided one
+constexpr rt_vdenoise_params kVDefaults = {4, 4.0f, 0.5f, 0.25f};
+
+int validate_vdenoise(int W, int H, const rt_vdenoise_params* p)
+{
+    const int rc = validate_frame_size(W, H);
+    if (rc) return rc;
+    if (!p) return fail(RT_EINVAL, "vdenoise: params is NULL");
+    const float sig[3] = {p->sigma_luminance, p->sigma_normal, p->sigma_albedo};
+    const char* const name[3] = {"sigma_luminance", "sigma_normal", "sigma_albedo"};
+    return validate_passes(p->iterations, 0, sig, name);
 }
 
 }  // namespace
@@ -164,6 +192,85 @@ void rt_denoise_atrous(int largeur_image, int hauteur_image, rt_color* canva, rt
         p = g_denoise_params;
     }
     (void)rt_denoise_host(largeur_image, hauteur_image, canva, albedo, normal, &p);
+}
+
+void rt_vdenoise_params_init(rt_vdenoise_params* p)
+{
+    if (p) *p = kVDefaults;
+}
+
+size_t rt_vdenoise_workspace_bytes(int W, int H)
+{
+    if (W < 1 || H < 1 || (long long)W * H > (1ll << 30)) return 0;
+    const long long npx = (long long)W * H;
+    return (4 * denoise_plane_floats(npx) + 3 * vdenoise_scalar_floats(npx)) * sizeof(float);
+}
+
+int rt_vdenoise_async(int W, int H, const double* d_sums_a, const double* d_sums_b, int spp_half,
+                      const rt_vdenoise_params* params, void* workspace, size_t workspace_bytes, const rt_frame* out,
+                      void* hip_stream)
+{
+    const int rc = validate_vdenoise(W, H, params);
+    if (rc) return rc;
+    if (!d_sums_a || !d_sums_b) return fail(RT_EINVAL, "vdenoise: an accumulator is NULL");
+    if (spp_half < 1) return fail(RT_EINVAL, "vdenoise: spp_half %d < 1", spp_half);
+    if (!out || !out->canva) return fail(RT_EINVAL, "vdenoise: out.canva is NULL");
+    if (!workspace) return fail(RT_EINVAL, "vdenoise: workspace is NULL");
+    if ((uintptr_t)workspace % 16) return fail(RT_EINVAL, "vdenoise: workspace is not 16-byte aligned");
+    if (workspace_bytes < rt_vdenoise_workspace_bytes(W, H))
+        return fail(RT_EINVAL, "vdenoise: workspace of %zu bytes, %dx%d needs %zu", workspace_bytes, W, H,
+                    rt_vdenoise_workspace_bytes(W, H));
+    const int e = launch_vdenoise(W, H, d_sums_a, d_sums_b, spp_half, params->iterations, params->sigma_luminance,
+                                  params->sigma_normal, params->sigma_albedo, (float*)workspace, (double*)out->canva,
+                                  (double*)out->albedo, (double*)out->normal, (double*)out->radiance, hip_stream);
+    if (e) return fail(RT_EDEVICE, "vdenoise launch: %s", hipGetErrorString((hipError_t)e));
+    return RT_OK;
+}
+
+int rt_render_vdenoised(const rt_scene* scene, const rt_params* params, const rt_vdenoise_params* vparams,
+                        rt_color* canva, rt_color* albedo, rt_color* normal)
+{
+    int rc, dev;
+    if ((rc = validate_scene(scene)) || (rc = validate_params(params))) return rc;
+    const int W = params->largeur_image, H = params->hauteur_image, S = params->nbRayonParPixel;
+    if ((rc = validate_vdenoise(W, H, vparams))) return rc;
+    if (!canva) return fail(RT_EINVAL, "vdenoise: canva is NULL");
+    if (S < 2 || S % 2) return fail(RT_EINVAL, "vdenoise: nbRayonParPixel %d is not even and >= 2", S);
+    if ((rc = first_device(dev))) return rc;
+    std::shared_ptr<rt_device_scene> sc;
+    if ((rc = scene_cache_get(dev, scene, sc))) return rc;
+    StreamLease ps;                  // drained on every return: the caller reads canva next
+    if ((rc = ps.acquire(dev, true))) return rc;
+    DeviceGuard g(dev);
+    const size_t npx = (size_t)W * H, plane = npx * sizeof(rt_color), sums = npx * 9 * sizeof(double);
+    const size_t ws_bytes = rt_vdenoise_workspace_bytes(W, H);
+    rt_color* const dst[3] = {canva, albedo, normal};
+    StreamBuffer dbuf;               // device: the two accumulators, the workspace, then the output planes
+    hipError_t e = ps->reserve_host(3 * plane);
+    if (e == hipSuccess) e = dbuf.alloc(2 * sums + ws_bytes + 3 * plane, ps->st, dev);
+    if (e != hipSuccess) return fail(RT_ENOMEM, "vdenoise buffers: %s", hipGetErrorString(e));
+    char* buf = (char*)dbuf.p;
+    double* acc[2] = {(double*)buf, (double*)(buf + sums)};
+    char* planes = buf + 2 * sums + ws_bytes;
+    if ((e = hipMemsetAsync(buf, 0, 2 * sums, ps->st)) != hipSuccess)
+        return fail(RT_EDEVICE, "vdenoise clear: %s", hipGetErrorString(e));
+    rt_params half = *params;
+    half.nbRayonParPixel = S / 2;
+    const rt_tiling whole = {0, H, 0, 1, 1};
+    for (int k = 0; k < 2; ++k)
+        if ((rc = rt_accumulate_async(sc.get(), &half, (long long)k * (S / 2), &whole, acc[k], ps->st))) return rc;
+    const rt_frame fr = {(rt_color*)planes, albedo ? (rt_color*)(planes + plane) : nullptr,
+                         normal ? (rt_color*)(planes + 2 * plane) : nullptr, nullptr};
+    if ((rc = rt_vdenoise_async(W, H, acc[0], acc[1], S / 2, vparams, buf + 2 * sums, ws_bytes, &fr, ps->st)))
+        return rc;
+    for (int pl = 0; pl < 3 && e == hipSuccess; ++pl)
+        if (dst[pl])
+            e = hipMemcpyAsync((char*)ps->host + pl * plane, planes + pl * plane, plane, hipMemcpyDeviceToHost, ps->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(ps->st);
+    if (e != hipSuccess) return fail(RT_EDEVICE, "vdenoise: %s", hipGetErrorString(e));
+    for (int pl = 0; pl < 3; ++pl)
+        if (dst[pl]) std::memcpy(dst[pl], (char*)ps->host + pl * plane, plane);
+    return RT_OK;
 }
 
 }  // extern "C"

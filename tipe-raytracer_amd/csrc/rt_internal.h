@@ -203,5 +203,12 @@ size_t denoise_plane_floats(long long npx);
 int launch_denoise(int W, int H, double* canva, const double* albedo, const double* normal, int iterations,
                    float sigma_color, float sigma_normal, float sigma_albedo, float* workspace, float* color3_out,
                    void* stream);
+// launchers (rt_vdenoise.hip): the variance-guided denoiser (rt.h "variance-guided denoiser") on two device
+// accumulators.  The workspace holds four planes of denoise_plane_floats(W*H) floats, then three of
+// vdenoise_scalar_floats(W*H); albedo / normal / radiance may be null.
+size_t vdenoise_scalar_floats(long long npx);
+int launch_vdenoise(int W, int H, const double* sums_a, const double* sums_b, int spp_half, int iterations,
+                    float sigma_luminance, float sigma_normal, float sigma_albedo, float* workspace, double* canva,
+                    double* albedo, double* normal, double* radiance, void* stream);
 
 }  // namespace rt

@@ -6,11 +6,13 @@
  *
  *   rt_demo [-w W] [-s spp] [-b nbRebondMax] [-ao AO_intensity] [-o out.ppm]
  *           [-obj file.obj -mtl file.mtl [-move x y z]] [-devices N]
- *           [-denoise [iterations]]
+ *           [-denoise [iterations]] [-vdenoise [iterations]]
  *
  * -denoise installs the library's built-in a-trous filter (rt_denoise_atrous;
  * not OIDN, and biased: meant for low-spp frames) as the denoiser hook before
  * the render, with `iterations` passes (default 4; more for larger frames).
+ * -vdenoise renders through rt_render_vdenoised instead: the variance-guided
+ * denoiser over the frame's two sample halves (spp must be even; one device).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -28,6 +30,9 @@ int main(int argc, char** argv)
     int W = 400, spp = 100, bounces = 5, ndev = 1, useAO = 0, denoise = 0;
     rt_denoise_params dn;
     rt_denoise_params_init(&dn);
+    int vdenoise = 0;
+    rt_vdenoise_params vdn;
+    rt_vdenoise_params_init(&vdn);
     double AO = 2.5, mx = 0, my = 0, mz = 0;
     const char *out = "render.ppm", *obj = NULL, *mtl = NULL;
     for (int i = 1; i < argc; i++) {
@@ -42,13 +47,17 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "-denoise")) {
             denoise = 1;
             if (i + 1 < argc && argv[i + 1][0] != '-') dn.iterations = atoi(argv[++i]);
+        } else if (!strcmp(argv[i], "-vdenoise")) {
+            vdenoise = 1;
+            if (i + 1 < argc && argv[i + 1][0] != '-') vdn.iterations = atoi(argv[++i]);
         } else if (!strcmp(argv[i], "-move") && i + 3 < argc) {
             mx = atof(argv[++i]);
             my = atof(argv[++i]);
             mz = atof(argv[++i]);
         } else {
             fprintf(stderr, "usage: %s [-w W] [-s spp] [-b bounces] [-ao I] [-o out.ppm] "
-                            "[-obj f.obj -mtl f.mtl [-move x y z]] [-devices N] [-denoise [iterations]]\n",
+                            "[-obj f.obj -mtl f.mtl [-move x y z]] [-devices N] [-denoise [iterations]] "
+                            "[-vdenoise [iterations]]\n",
                     argv[0]);
             return 2;
         }
@@ -119,9 +128,10 @@ int main(int argc, char** argv)
     rt_color* normal = (rt_color*)calloc(n, sizeof(rt_color));
     struct timeval t0, t1;
     gettimeofday(&t0, NULL);
-    int rc = rt_render_rows(&scene, &p, H - 1, 0, canva, albedo, normal);
+    int rc = vdenoise ? rt_render_vdenoised(&scene, &p, &vdn, canva, albedo, normal)
+                      : rt_render_rows(&scene, &p, H - 1, 0, canva, albedo, normal);
     gettimeofday(&t1, NULL);
-    if (rc) { fprintf(stderr, "rt_render_rows: %s\n", rt_last_error()); return 1; }
+    if (rc) { fprintf(stderr, "%s: %s\n", vdenoise ? "rt_render_vdenoised" : "rt_render_rows", rt_last_error()); return 1; }
     double dt = (t1.tv_sec - t0.tv_sec) + 1e-6 * (t1.tv_usec - t0.tv_usec);
     fprintf(stderr, "%dx%d, %d spp, %d bounces: %.3f s, %.1f Msamples/s (end-to-end)\n", W, H, spp, bounces, dt,
             (double)n * spp / dt / 1e6);

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from .types import (Vec3, Ray, Material, Sphere, UV, Triangle, Camera, ThreadData, Scene,  # noqa: F401
-                    Params, Tiling, Frame, DenoiseParams, RT_OK, RT_EINVAL, RT_EDEVICE, RT_ENOMEM, RT_EUNSUPPORTED,
+                    Params, Tiling, Frame, DenoiseParams, VDenoiseParams, RT_OK, RT_EINVAL, RT_EDEVICE, RT_ENOMEM, RT_EUNSUPPORTED,
                     RT_RNG_PHILOX, RT_RNG_GLIBC, RT_NCOUNTERS, COUNTER_NAMES, RT_SPP_CHUNKS_AUTO,
                     RT_SPP_CHUNKS_DEFAULT)
 
@@ -96,6 +96,15 @@ def lib():
         L.rt_denoise_atrous.argtypes = [C.c_int, C.c_int, C.c_void_p, Camera, C.c_void_p, C.c_void_p]
         L.rt_denoise_atrous.restype = None
         L.rt_set_denoise_params.argtypes = [P(DenoiseParams)]
+        if hasattr(L, "rt_vdenoise_async"):      # (added to ABI 5: older builds in A/B runs lack it)
+            L.rt_vdenoise_params_init.argtypes = [P(VDenoiseParams)]
+            L.rt_vdenoise_params_init.restype = None
+            L.rt_vdenoise_workspace_bytes.argtypes = [C.c_int, C.c_int]
+            L.rt_vdenoise_workspace_bytes.restype = C.c_size_t
+            L.rt_vdenoise_async.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, P(VDenoiseParams),
+                                            C.c_void_p, C.c_size_t, P(Frame), C.c_void_p]
+            L.rt_render_vdenoised.argtypes = [P(Scene), P(Params), P(VDenoiseParams), C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
         _lib = L
     return _lib
 
@@ -108,7 +117,9 @@ EXPORTED_SYMBOLS = ["rt_params_init", "rt_init", "rt_shutdown", "rt_last_error",
                     "rt_verify_sphere_pass", "rt_verify_normalize", "rt_verify_texel_map", "rt_set_zero_throughput_exit", "rt_set_fill_spp_chunks", "rt_set_fill_precision",
                     "rt_scene_cache_clear", "rt_gather_async", "rt_render_gather_async", "rt_peer_access",
                     "rt_last_render_kernel", "rt_denoise_params_init", "rt_denoise_workspace_bytes",
-                    "rt_denoise_async", "rt_denoise_host", "rt_denoise_atrous", "rt_set_denoise_params"]
+                    "rt_denoise_async", "rt_denoise_host", "rt_denoise_atrous", "rt_set_denoise_params",
+                    "rt_vdenoise_params_init", "rt_vdenoise_workspace_bytes", "rt_vdenoise_async",
+                    "rt_render_vdenoised"]
 
 # rt_denoise_fn (rt.h): denoiser()'s signature, denoiser.h:31
 DENOISE_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p, Camera, C.c_void_p, C.c_void_p)
@@ -201,6 +212,40 @@ def set_denoise_atrous(enable=True, params=None):
     check(lib().rt_set_denoise_params(None if params is None else C.byref(params)))
     _hook_ref = C.cast(lib().rt_denoise_atrous, DENOISE_FN) if enable else DENOISE_FN()
     lib().rt_set_denoise_hook(_hook_ref)
+
+
+def vdenoise_params(iterations=None, sigma_luminance=None, sigma_normal=None, sigma_albedo=None):
+    """rt_vdenoise_params_init's defaults (4 passes; sigmas 4, 0.5, 0.25) with the given fields replaced."""
+    p = VDenoiseParams()
+    lib().rt_vdenoise_params_init(C.byref(p))
+    for name, v in (("iterations", iterations), ("sigma_luminance", sigma_luminance), ("sigma_normal", sigma_normal),
+                    ("sigma_albedo", sigma_albedo)):
+        if v is not None:
+            setattr(p, name, v)
+    return p
+
+
+def vdenoise_async(W, H, sums_a_ptr, sums_b_ptr, spp_half, params, workspace_ptr, workspace_bytes, canva_ptr,
+                   albedo_ptr=None, normal_ptr=None, radiance_ptr=None, stream=None):
+    """rt_vdenoise_async: the variance-guided denoiser (rt.h) on two device
+    accumulators of spp_half samples each, into device planes."""
+    fr = Frame(canva_ptr, albedo_ptr, normal_ptr, radiance_ptr)
+    check(lib().rt_vdenoise_async(W, H, sums_a_ptr, sums_b_ptr, spp_half, C.byref(params), workspace_ptr,
+                                  workspace_bytes, C.byref(fr), stream))
+
+
+def render_vdenoised(scene, params, vparams=None, albedo=True, normal=True):
+    """rt_render_vdenoised into fresh (H, W, 3) float64 arrays (canva, albedo,
+    normal): the frame's two sample halves rendered and filtered on the device."""
+    W, H = params.largeur_image, params.hauteur_image
+    canva = np.zeros((H, W, 3))
+    alb = np.zeros((H, W, 3)) if albedo else None
+    nrm = np.zeros((H, W, 3)) if normal else None
+    vp = vparams if vparams is not None else vdenoise_params()
+    check(lib().rt_render_vdenoised(C.byref(scene), C.byref(params), C.byref(vp), canva.ctypes.data,
+                                    alb.ctypes.data if alb is not None else None,
+                                    nrm.ctypes.data if nrm is not None else None))
+    return canva, alb, nrm
 
 
 def last_gather_transport():

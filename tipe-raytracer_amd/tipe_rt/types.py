@@ -151,5 +151,11 @@ class DenoiseParams(C.Structure):
                 ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float)]
 
 
+class VDenoiseParams(C.Structure):
+    """rt.h rt_vdenoise_params: the variance-guided denoiser over two half-sample accumulators."""
+    _fields_ = [("iterations", C.c_int), ("sigma_luminance", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float)]
+
+
 assert C.sizeof(Vec3) == 24 and C.sizeof(Material) == 80 and C.sizeof(Sphere) == 112
 assert C.sizeof(Triangle) == 200 and C.sizeof(Camera) == 96 and C.sizeof(ThreadData) == 248

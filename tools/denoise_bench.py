@@ -1,13 +1,22 @@
 #!/usr/bin/env python3
-"""Time the built-in denoiser (rt_denoise_async) on device-resident frames.
+"""Time the built-in denoisers (rt_denoise_async, rt_vdenoise_async) on device-resident frames.
 
     tools/denoise_bench.py [--sizes 1200x900,3840x2880] [--iterations 5] [--reps 20] [--warmup 3] [--label TAG]
+                           [--filter atrous|vdenoise|both] [--rounds 1]
 
-Seeded random planes (the tests' distribution); per size one JSON line with
-the mean call time from device events, the compulsory bytes of one pass (48 B
-per pixel: three float3 planes read, one written) and a SHA-1 of the filtered
-canva, so two builds can be compared on what they compute as well as on how
-fast.  Per-pass kernel times come from running this under
+Seeded random inputs (the tests' distributions); per size, round and filter
+one JSON line with the mean call time from device events, the compulsory
+bytes of one pass and a SHA-1 of the filtered canva, so two builds can be
+compared on what they compute as well as on how fast.
+  atrous    rt_denoise_async on random planes; 48 B per pixel and pass (three
+            float3 planes read, one written); the call time includes the copy
+            that restores the canva it filters in place.
+  vdenoise  rt_vdenoise_async on two random accumulators (radiance in [0, 4] n,
+            albedo in [0, 1] n, normal in [-1, 1] n, n = --spp-half); 68 B per
+            pixel and pass (the pass reads c, v, a, nn and L and writes c and
+            v: 60 B; the variance blur reads v and writes L: 8 B).
+  both      the two alternate, round by round, in one process.
+Per-pass kernel times come from running this under
 `rocprofv3 --kernel-trace --stats` (a run of its own) and
 tools/denoise_trace_summary.py."""
 import argparse
@@ -27,16 +36,20 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--label", default="")
+    ap.add_argument("--filter", choices=("atrous", "vdenoise", "both"), default="atrous")
+    ap.add_argument("--rounds", type=int, default=1)
+    ap.add_argument("--spp-half", type=int, default=8)
     args = ap.parse_args()
     import torch
     import tipe_rt
     if not torch.cuda.is_available():
         sys.exit("denoise_bench: needs a GPU (no CPU fallback)")
     dev = torch.device("cuda:0")
-    params = tipe_rt.denoise_params(iterations=args.iterations)
     stream = torch.cuda.current_stream().cuda_stream
-    for size in args.sizes.split(","):
-        W, H = (int(v) for v in size.split("x"))
+
+    def atrous(W, H):
+        """(call, canva, extra fields of the JSON line)"""
+        params = tipe_rt.denoise_params(iterations=args.iterations)
         g = torch.Generator(device=dev).manual_seed(W * 10007 + H)
         canva0 = torch.randint(0, 256, (H, W, 3), generator=g, device=dev).to(torch.float64)
         albedo = torch.rand((H, W, 3), generator=g, device=dev, dtype=torch.float64)
@@ -50,20 +63,47 @@ def main():
             tipe_rt.denoise_async(W, H, canva.data_ptr(), albedo.data_ptr(), normal.data_ptr(), params,
                                   ws.data_ptr(), nbytes, None, stream)
 
-        for _ in range(args.warmup):
-            call()
+        return call, canva, "call_ms_incl_frame_copy", 48 * W * H
+
+    def vdenoise(W, H):
+        params = tipe_rt.vdenoise_params(iterations=args.iterations)
+        n = args.spp_half
+        g = torch.Generator(device=dev).manual_seed(W * 10007 + H + 1)
+        lo = torch.tensor([0.0] * 6 + [-1.0] * 3, dtype=torch.float64, device=dev)
+        hi = torch.tensor([4.0] * 3 + [1.0] * 6, dtype=torch.float64, device=dev)
+        acc = [(lo + (hi - lo) * torch.rand((H, W, 9), generator=g, device=dev, dtype=torch.float64)) * n
+               for _ in range(2)]
+        nbytes = tipe_rt.lib().rt_vdenoise_workspace_bytes(W, H)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        canva = torch.zeros((H, W, 3), dtype=torch.float64, device=dev)
+
+        def call():
+            tipe_rt.vdenoise_async(W, H, acc[0].data_ptr(), acc[1].data_ptr(), n, params, ws.data_ptr(), nbytes,
+                                   canva.data_ptr(), stream=stream)
+
+        return call, canva, "call_ms", 68 * W * H
+
+    filters = {"atrous": [atrous], "vdenoise": [vdenoise], "both": [atrous, vdenoise]}[args.filter]
+    for size in args.sizes.split(","):
+        W, H = (int(v) for v in size.split("x"))
+        made = [(f.__name__,) + f(W, H) for f in filters]
+        for _, call, _, _, _ in made:
+            for _ in range(args.warmup):
+                call()
         torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(args.reps):
-            call()
-        t1.record()
-        torch.cuda.synchronize()
-        ms = t0.elapsed_time(t1) / args.reps
-        digest = hashlib.sha1(canva.cpu().numpy().tobytes()).hexdigest()
-        print(json.dumps({"label": args.label, "W": W, "H": H, "iterations": args.iterations, "reps": args.reps,
-                          "call_ms_incl_frame_copy": round(ms, 4), "pass_compulsory_bytes": 48 * W * H,
-                          "canva_sha1": digest}), flush=True)
+        for rnd in range(args.rounds):
+            for name, call, canva, key, nbytes_pass in made:
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                for _ in range(args.reps):
+                    call()
+                t1.record()
+                torch.cuda.synchronize()
+                ms = t0.elapsed_time(t1) / args.reps
+                digest = hashlib.sha1(canva.cpu().numpy().tobytes()).hexdigest()
+                print(json.dumps({"label": args.label, "filter": name, "round": rnd, "W": W, "H": H,
+                                  "iterations": args.iterations, "reps": args.reps, key: round(ms, 4),
+                                  "pass_compulsory_bytes": nbytes_pass, "canva_sha1": digest}), flush=True)
 
 
 if __name__ == "__main__":
