@@ -45,7 +45,10 @@ extern "C" {
  *    Added to 5 without a new number (nothing existing changed; a caller
  *    detects them by symbol): the variance-guided denoiser over two
  *    half-sample accumulators (rt_vdenoise_params, rt_vdenoise_params_init,
- *    rt_vdenoise_workspace_bytes, rt_vdenoise_async, rt_render_vdenoised).
+ *    rt_vdenoise_workspace_bytes, rt_vdenoise_async, rt_render_vdenoised);
+ *    adaptive sampling (rt_accumulate_list_async, rt_adaptive_select_async,
+ *    rt_adaptive_workspace_bytes, rt_adaptive_params, rt_adaptive_params_init,
+ *    rt_adaptive_async, rt_resolve_adaptive_async, rt_render_adaptive).
  * A caller compares rt_abi_version() with the RT_ABI_VERSION it was built
  * against before passing rt_params or counter arrays.                   */
 #define RT_ABI_VERSION 5
@@ -603,6 +606,118 @@ int rt_vdenoise_async(int W, int H, const double* d_sums_a, const double* d_sums
  * when not NULL, are written only on success (W*H colours each). */
 int rt_render_vdenoised(const rt_scene* scene, const rt_params* params, const rt_vdenoise_params* vparams,
                         rt_color* canva, rt_color* albedo, rt_color* normal);
+
+/* ---- adaptive sampling: per-pixel sample counts from the two-half variance - */
+/* A render that spends samples by its own error estimate: two accumulators
+ * cover disjoint halves of a pixel's samples (the dual-buffer estimate of the
+ * variance-guided denoiser above), a selection pass marks the pixels whose
+ * estimated displayed error is within a tolerance as settled, and the next
+ * round renders the others only.  The stream is keyed by (pixel, sample
+ * index), so a pixel that received samples [0, n) holds exactly the sums a
+ * whole-frame render of n samples gives it, whatever its neighbours received:
+ * every step below is defined by rt_accumulate_async / rt_resolve_async or by
+ * the text here, bit for bit.  Three layers, each usable on its own.
+ *
+ * 1. Samples for listed pixels.  rt_accumulate_list_async adds samples
+ * [sample_offset, sample_offset + nbRayonParPixel) of pixel d_list[e], for
+ * each e < min(*d_count, list_cap), to d_sums: the full-frame accumulator of
+ * W*H*9 doubles, as rt_accumulate_async's with the whole-frame tiling
+ * {0, H, 0, 1, 1}.  d_list is a device array of global pixel indices j*W+i,
+ * strictly ascending; d_count is a device word that the kernels read: the
+ * host never reads it and the call does not synchronise.  list_cap sizes the
+ * launch.  The result for a listed pixel is rt_accumulate_async's for the same
+ * params and offset: with spp_chunks 1 the running fold continues in sample
+ * order, with P > 1 the batch's P slice sums (rt_resolve_spp_chunks,
+ * rt_chunk_bound on the batch's own sample count) are added in slice order.
+ * A pixel that is not listed is not written at all (nor is anything for an
+ * entry that is not below W*H).  With P > 1 the list is rendered in bands of
+ * entries that reuse one stream-ordered buffer of partial sums, sized for
+ * list_cap entries and at most 512 MiB; bands change no result.  RT_SEM_CUDA is RT_EUNSUPPORTED; a NULL
+ * pointer, list_cap of 0 or above W*H, or a sample range beyond 2^32 is
+ * RT_EINVAL, before any device work. */
+int rt_accumulate_list_async(const rt_device_scene* scene, const rt_params* params, long long sample_offset,
+                             const unsigned* d_list, const unsigned* d_count, unsigned list_cap,
+                             double* d_sums, void* hip_stream);
+
+/* 2. Which pixels go on.  rt_adaptive_select_async is IEEE binary32 with only
+ * + - * / and no contraction, except where "double" is written, so a float32
+ * restatement of this text equals the GPU bit for bit.
+ *
+ * The active pixels on entry are d_list[0 .. *d_count), or every pixel when
+ * round == 0 (the list is then ignored and overwritten).  A and B hold
+ * n = n_half samples per active pixel each.  For each active pixel p:
+ *   rap = 1.0 / n                                   (double)
+ *   mX  = (float)(rap * X)  for the three radiance sums X of A and of B
+ *   c = 0.5f * (mA + mB)      d = 0.5f * (mA - mB)
+ *   v[p] = (0.25f*(d0*d0) + 0.5f*(d1*d1)) + 0.25f*(d2*d2)     (the denoiser's v)
+ *   y[p] = (0.25f*c0 + 0.5f*c1) + 0.25f*c2
+ * v and y are planes of the workspace that persist between calls: an inactive
+ * pixel keeps the value of its last active round.  After every active v is
+ * written, each active pixel forms vb, the 3x3 blur of the v plane exactly as
+ * the denoiser's text has it: g = {1/4, 1/2, 1/4}, dy = -1..1 (outer), dx =
+ * -1..1 (inner), neighbours inside the image only, gg = g[dy]*g[dx],
+ * bn += gg * v[q], bd += gg, both from +0.0f, vb = bn / bd.  The pixel is
+ * settled iff
+ *   vb <= ((4.0f * (tolerance*tolerance)) * (y[p] + 0x1p-8f))
+ * (the canva is sqrt(c), so the displayed error is about sigma / (2 sqrt(y));
+ * the test asks for that to be at most `tolerance`; the floor 2^-8 keeps black
+ * pixels from running forever; a NaN compares false and runs on).
+ * d_rounds[p] = round + 1 for every active pixel; the pixels that are active
+ * and not settled, in ascending order, become the new d_list and *d_count
+ * (d_list holds up to W*H entries).  The order is deterministic: flags, block
+ * counts, one scan, a scatter; no kernel waits on another block.
+ * RT_EINVAL before any device work for W or H < 1 or a frame above 2^30
+ * pixels, a NULL pointer, n_half < 1, round outside 0..15, a tolerance that
+ * is not finite or outside [2^-12, 1], a workspace smaller than
+ * rt_adaptive_workspace_bytes(W, H) or not 16-byte aligned. */
+int rt_adaptive_select_async(int W, int H, const double* d_sums_a, const double* d_sums_b, int n_half,
+                             float tolerance, int round, unsigned* d_list, unsigned* d_count,
+                             int* d_rounds, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* Bytes of device scratch for a W x H frame (0 for W or H below 1 or a frame
+ * above 2^30 pixels): the selection pass's planes and, behind them,
+ * rt_adaptive_async's list and count.  Its layout is private. */
+size_t rt_adaptive_workspace_bytes(int W, int H);
+
+/* 3. The loop.  params->nbRayonParPixel is ignored: the schedule sets every
+ * batch's size.  With b_0 = first_half and n_r = first_half * 2^r samples per
+ * accumulator after round r, round r adds samples [o_r, o_r + b_r) to A and
+ * [o_r + b_r, o_r + 2 b_r) to B, where o_0 = 0 and, for r >= 1, b_r = n_(r-1)
+ * and o_r = 2 n_(r-1); then it runs the selection with n_half = n_r.  A pixel
+ * that took k rounds therefore holds exactly samples [0, 2 n_(k-1)).  Round 0
+ * is two rt_accumulate_async calls on the whole frame after zeroing A and B;
+ * rounds >= 1 are rt_accumulate_list_async calls with list_cap = W*H; the
+ * last round only sets d_rounds.  All max_rounds rounds are always enqueued
+ * (an empty list costs empty launches): there is no host read-back and no
+ * synchronisation.  d_rounds (W*H ints) receives each pixel's round count k;
+ * `frame`, when not NULL, then receives rt_resolve_adaptive_async's planes.
+ * RT_EINVAL before any device work for first_half < 1, max_rounds outside
+ * 1..16 or first_half * 2^max_rounds above 2^31, a tolerance as above, a NULL
+ * accumulator, d_rounds or workspace, a workspace too small or misaligned;
+ * RT_SEM_CUDA is RT_EUNSUPPORTED. */
+typedef struct rt_adaptive_params {
+    int first_half;                              /* samples per accumulator in round 0, >= 1 */
+    int max_rounds;                              /* 1..16 */
+    float tolerance;                             /* finite, within [2^-12, 1] */
+} rt_adaptive_params;
+/* Defaults: first_half 8, max_rounds 5, tolerance 1/64. */
+void rt_adaptive_params_init(rt_adaptive_params* p);
+int rt_adaptive_async(const rt_device_scene* scene, const rt_params* params, const rt_adaptive_params* aparams,
+                      double* d_sums_a, double* d_sums_b, int* d_rounds, void* workspace, size_t workspace_bytes,
+                      const rt_frame* frame, void* hip_stream);
+/* Per pixel with k = d_rounds[p]: s = A + B per sum (double), then
+ * rt_resolve_async's operations on s with total_spp = 2 * first_half * 2^(k-1)
+ * (canva required; albedo, normal and radiance = s / total_spp when given). */
+int rt_resolve_adaptive_async(int W, int H, const double* d_sums_a, const double* d_sums_b, const int* d_rounds,
+                              int first_half, const rt_frame* frame, void* hip_stream);
+/* The whole frame on rt_init's first device, as rt_render_vdenoised: cached
+ * scene, pooled stream, pinned staging; canva, albedo / normal and rounds
+ * (W*H ints) when not NULL are written only on success.
+ *
+ * Out of scope: rt_vdenoise_async takes one spp_half for the frame, so it
+ * cannot yet filter an adaptive result; cyclic tiles and multi-device
+ * rendering; RT_SEM_CUDA; running the list on the task-queue kernel. */
+int rt_render_adaptive(const rt_scene* scene, const rt_params* params, const rt_adaptive_params* aparams,
+                       rt_color* canva, rt_color* albedo, rt_color* normal, int* rounds);
 
 /* Device-math self test: evaluates one device primitive on n host inputs
  * (synchronous, device 0).  op: 0 acos, 1 sinf, 2 cosf, 3 pow(x, y),

@@ -1,0 +1,315 @@
+// rt_adaptive_api.cpp — adaptive sampling's entry points of the C-ABI (rt.h
+// "adaptive sampling"; kernels: rt_adaptive.hip): samples for a list of pixels
+// (rt_accumulate_list_async), the selection pass (rt_adaptive_select_async),
+// the loop over both (rt_adaptive_async), its resolve
+// (rt_resolve_adaptive_async) and the whole-frame render into host arrays
+// (rt_render_adaptive).
+#include <cmath>
+#include <cstring>
+
+#include "rt_host_slots.h"
+
+using namespace rt;
+
+namespace {
+
+constexpr rt_adaptive_params kDefaults = {8, 5, 1.0f / 64.0f};
+
+// The private workspace of the selection pass (rt_adaptive_workspace_bytes),
+// byte offsets: the v and y planes, the keep plane (each padded to whole
+// blocks of 256 entries), the block counts, the recorded incoming count; then
+// rt_adaptive_async's list and its count.
+struct Layout {
+    size_t v, y, keep, counts, n_in, list, count, total;
+};
+Layout layout_of(long long npx)
+{
+    const size_t plane = (size_t)adaptive_blocks(npx) * 256 * sizeof(unsigned);
+    const size_t cbytes = ((size_t)adaptive_blocks(npx) * sizeof(unsigned) + 15) / 16 * 16;
+    Layout l;
+    l.v = 0;
+    l.y = plane;
+    l.keep = 2 * plane;
+    l.counts = 3 * plane;
+    l.n_in = l.counts + cbytes;
+    l.list = l.n_in + 16;
+    l.count = l.list + plane;
+    l.total = l.count + 16;
+    return l;
+}
+
+int validate_frame(int W, int H)
+{
+    if (W < 1 || H < 1) return fail(RT_EINVAL, "adaptive: frame %dx%d", W, H);
+    if ((long long)W * H > (1ll << 30)) return fail(RT_EINVAL, "adaptive: frame %dx%d above 2^30 pixels", W, H);
+    return RT_OK;
+}
+
+int validate_tolerance(float t)
+{
+    if (!std::isfinite(t)) return fail(RT_EINVAL, "adaptive: tolerance is not finite");
+    if (t < 0x1p-12f || t > 1.0f) return fail(RT_EINVAL, "adaptive: tolerance %g outside [2^-12, 1]", (double)t);
+    return RT_OK;
+}
+
+int validate_workspace(int W, int H, const void* workspace, size_t workspace_bytes)
+{
+    if (!workspace) return fail(RT_EINVAL, "adaptive: workspace is NULL");
+    if ((uintptr_t)workspace % 16) return fail(RT_EINVAL, "adaptive: workspace is not 16-byte aligned");
+    if (workspace_bytes < rt_adaptive_workspace_bytes(W, H))
+        return fail(RT_EINVAL, "adaptive: workspace of %zu bytes, %dx%d needs %zu", workspace_bytes, W, H,
+                    rt_adaptive_workspace_bytes(W, H));
+    return RT_OK;
+}
+
+int validate_adaptive(const rt_adaptive_params* a)
+{
+    if (!a) return fail(RT_EINVAL, "adaptive: adaptive params is NULL");
+    if (a->first_half < 1) return fail(RT_EINVAL, "adaptive: first_half %d < 1", a->first_half);
+    if (a->max_rounds < 1 || a->max_rounds > 16)
+        return fail(RT_EINVAL, "adaptive: max_rounds %d outside 1..16", a->max_rounds);
+    if (((long long)a->first_half << a->max_rounds) > (1ll << 31))   // 2 n_{R-1} = first_half 2^R
+        return fail(RT_EINVAL, "adaptive: %d x 2^%d samples per pixel exceed 2^31", a->first_half, a->max_rounds);
+    return validate_tolerance(a->tolerance);
+}
+
+AdaptiveSelect select_args(int W, int H, void* workspace)
+{
+    const Layout l = layout_of((long long)W * H);
+    char* ws = (char*)workspace;
+    AdaptiveSelect s;
+    std::memset(&s, 0, sizeof s);
+    s.W = W;
+    s.H = H;
+    s.npx = (unsigned)W * (unsigned)H;
+    s.v = (float*)(ws + l.v);
+    s.y = (float*)(ws + l.y);
+    s.keep = (unsigned*)(ws + l.keep);
+    s.counts = (unsigned*)(ws + l.counts);
+    s.n_in = (unsigned*)(ws + l.n_in);
+    return s;
+}
+
+// Every band of a list launch as plan_list (rt_launch_plan.cpp) sizes them, with
+// its stream-ordered scratch (the uniform block and, for chunks > 1, one band's
+// partials, reused band after band).
+int launch_list_on_stream(KParams& kp, const double* uni, const unsigned* d_list, const unsigned* d_count,
+                          unsigned list_cap, hipStream_t st)
+{
+    const int rc = keep_pool_memory();
+    if (rc) return rc;
+    const RenderPlan plan = plan_render(kp, false);     // tree, width and sky (running sums: never the queue)
+    const ListPlan bands = plan_list(kp.chunks, list_cap);
+    const unsigned band = bands.band;
+    const size_t partial_bytes = bands.partial_bytes;
+    double* d_uni = nullptr;
+    double* d_part = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&d_uni, U_COUNT * sizeof(double), st));
+    UniBlock ub;
+    for (int i = 0; i < U_COUNT; ++i) ub.v[i] = uni[i];
+    hipError_t e = (hipError_t)launch_set_uniforms(ub, d_uni, st);
+    if (partial_bytes && e == hipSuccess) e = hipMallocAsync((void**)&d_part, partial_bytes, st);
+    kp.uni = d_uni;
+    kp.stack_cap = plan.stack_cap;
+    ListArgs la = {d_list, d_count, d_part, 0u, 0u, band};
+    for (unsigned long long e0 = 0; e == hipSuccess && e0 < list_cap; e0 += band) {
+        la.e0 = (unsigned)e0;
+        la.e1 = (unsigned)std::min<unsigned long long>(e0 + band, list_cap);
+        e = (hipError_t)launch_render_list(kp, plan, la, st);
+    }
+    if (d_part) (void)hipFreeAsync(d_part, st);
+    (void)hipFreeAsync(d_uni, st);
+    if (e != hipSuccess) return fail(RT_EDEVICE, "list render launch: %s", hipGetErrorString(e));
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_accumulate_list_async(const rt_device_scene* scene, const rt_params* params, long long sample_offset,
+                             const unsigned* d_list, const unsigned* d_count, unsigned list_cap, double* d_sums,
+                             void* hip_stream)
+{
+    if (!scene) return fail(RT_EINVAL, "scene is NULL");
+    int rc;
+    if ((rc = validate_params(params))) return rc;
+    if (params->semantics == RT_SEM_CUDA)
+        return fail(RT_EUNSUPPORTED, "rt_accumulate_list_async renders RT_SEM_MAIN_C only");
+    if (!d_list || !d_count || !d_sums) return fail(RT_EINVAL, "d_list, d_count or d_sums is NULL");
+    const unsigned long long npx = (unsigned long long)params->largeur_image * (unsigned long long)params->hauteur_image;
+    if (list_cap == 0 || list_cap > npx)
+        return fail(RT_EINVAL, "list_cap %u outside 1..%llu (the frame's pixels)", list_cap, npx);
+    if (sample_offset < 0 || sample_offset + params->nbRayonParPixel > (1ll << 32))
+        return fail(RT_EINVAL, "samples [%lld, %lld) exceed the 32-bit Philox sample word", sample_offset,
+                    sample_offset + params->nbRayonParPixel);
+    const rt_tiling whole = {0, params->hauteur_image, 0, 1, 1};
+    KParams kp;
+    double uni[U_COUNT];
+    fill_kparams(scene, params, &whole, kp, uni);
+    kp.sums = d_sums;
+    kp.s_base = sample_offset;
+    DeviceGuard guard(scene->device);
+    return launch_list_on_stream(kp, uni, d_list, d_count, list_cap, (hipStream_t)hip_stream);
+}
+
+size_t rt_adaptive_workspace_bytes(int W, int H)
+{
+    if (W < 1 || H < 1 || (long long)W * H > (1ll << 30)) return 0;
+    return layout_of((long long)W * H).total;
+}
+
+int rt_adaptive_select_async(int W, int H, const double* d_sums_a, const double* d_sums_b, int n_half,
+                             float tolerance, int round, unsigned* d_list, unsigned* d_count, int* d_rounds,
+                             void* workspace, size_t workspace_bytes, void* hip_stream)
+{
+    int rc;
+    if ((rc = validate_frame(W, H))) return rc;
+    if (!d_sums_a || !d_sums_b) return fail(RT_EINVAL, "adaptive: an accumulator is NULL");
+    if (!d_list || !d_count || !d_rounds) return fail(RT_EINVAL, "adaptive: d_list, d_count or d_rounds is NULL");
+    if (n_half < 1) return fail(RT_EINVAL, "adaptive: n_half %d < 1", n_half);
+    if (round < 0 || round > 15) return fail(RT_EINVAL, "adaptive: round %d outside 0..15", round);
+    if ((rc = validate_tolerance(tolerance)) || (rc = validate_workspace(W, H, workspace, workspace_bytes))) return rc;
+    AdaptiveSelect s = select_args(W, H, workspace);
+    s.all = round == 0;
+    s.sums_a = d_sums_a;
+    s.sums_b = d_sums_b;
+    s.rap = 1.0 / (double)n_half;
+    s.tolerance = tolerance;
+    s.round = round;
+    s.list = d_list;
+    s.count = d_count;
+    s.rounds = d_rounds;
+    const int e = launch_adaptive_select(s, hip_stream);
+    if (e) return fail(RT_EDEVICE, "adaptive select launch: %s", hipGetErrorString((hipError_t)e));
+    return RT_OK;
+}
+
+void rt_adaptive_params_init(rt_adaptive_params* p)
+{
+    if (p) *p = kDefaults;
+}
+
+int rt_resolve_adaptive_async(int W, int H, const double* d_sums_a, const double* d_sums_b, const int* d_rounds,
+                              int first_half, const rt_frame* frame, void* hip_stream)
+{
+    int rc;
+    if ((rc = validate_frame(W, H))) return rc;
+    if (!d_sums_a || !d_sums_b) return fail(RT_EINVAL, "adaptive: an accumulator is NULL");
+    if (!d_rounds) return fail(RT_EINVAL, "adaptive: d_rounds is NULL");
+    if (first_half < 1) return fail(RT_EINVAL, "adaptive: first_half %d < 1", first_half);
+    if (!frame || !frame->canva) return fail(RT_EINVAL, "adaptive: frame.canva is NULL");
+    const int e = launch_adaptive_resolve((long long)W * H, d_sums_a, d_sums_b, d_rounds, first_half,
+                                          (double*)frame->canva, (double*)frame->albedo, (double*)frame->normal,
+                                          (double*)frame->radiance, hip_stream);
+    if (e) return fail(RT_EDEVICE, "adaptive resolve launch: %s", hipGetErrorString((hipError_t)e));
+    return RT_OK;
+}
+
+int rt_adaptive_async(const rt_device_scene* scene, const rt_params* params, const rt_adaptive_params* aparams,
+                      double* d_sums_a, double* d_sums_b, int* d_rounds, void* workspace, size_t workspace_bytes,
+                      const rt_frame* frame, void* hip_stream)
+{
+    if (!scene) return fail(RT_EINVAL, "scene is NULL");
+    if (!params) return fail(RT_EINVAL, "params is NULL");
+    int rc;
+    if ((rc = validate_adaptive(aparams))) return rc;
+    rt_params batch = *params;                   // nbRayonParPixel is the schedule's, not the caller's
+    batch.nbRayonParPixel = aparams->first_half;
+    if ((rc = validate_params(&batch))) return rc;
+    if (batch.semantics == RT_SEM_CUDA) return fail(RT_EUNSUPPORTED, "rt_adaptive_async renders RT_SEM_MAIN_C only");
+    const int W = batch.largeur_image, H = batch.hauteur_image;
+    if ((rc = validate_frame(W, H))) return rc;
+    if (!d_sums_a || !d_sums_b) return fail(RT_EINVAL, "adaptive: an accumulator is NULL");
+    if (!d_rounds) return fail(RT_EINVAL, "adaptive: d_rounds is NULL");
+    if ((rc = validate_workspace(W, H, workspace, workspace_bytes))) return rc;
+    if (frame && !frame->canva) return fail(RT_EINVAL, "adaptive: frame.canva is NULL");
+
+    const hipStream_t st = (hipStream_t)hip_stream;
+    const long long npx = (long long)W * H;
+    const Layout l = layout_of(npx);
+    unsigned* d_list = (unsigned*)((char*)workspace + l.list);
+    unsigned* d_count = (unsigned*)((char*)workspace + l.count);
+    const rt_tiling whole = {0, H, 0, 1, 1};
+    double* acc[2] = {d_sums_a, d_sums_b};
+    DeviceGuard guard(scene->device);
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipMemsetAsync(acc[k], 0, (size_t)npx * 9 * sizeof(double), st));
+    const int R = aparams->max_rounds;
+    for (int r = 0; r < R; ++r) {
+        // b_r samples to each accumulator from o_r on; n_r per accumulator afterwards
+        const long long n_r = (long long)aparams->first_half << r;
+        const long long b = r == 0 ? n_r : n_r / 2, o = r == 0 ? 0 : n_r;
+        batch.nbRayonParPixel = (int)b;
+        for (int k = 0; k < 2; ++k) {
+            rc = r == 0 ? rt_accumulate_async(scene, &batch, o + k * b, &whole, acc[k], st)
+                        : rt_accumulate_list_async(scene, &batch, o + k * b, d_list, d_count, (unsigned)npx, acc[k], st);
+            if (rc) return rc;
+        }
+        if (r < R - 1) {
+            rc = rt_adaptive_select_async(W, H, d_sums_a, d_sums_b, (int)n_r, aparams->tolerance, r, d_list, d_count,
+                                          d_rounds, workspace, workspace_bytes, st);
+            if (rc) return rc;
+        } else {                                 // the last round selects nothing: its pixels' count only
+            AdaptiveSelect s = select_args(W, H, workspace);
+            s.all = r == 0;
+            s.list = d_list;
+            s.count = d_count;
+            s.rounds = d_rounds;
+            const int e = launch_adaptive_mark(s, R, st);
+            if (e) return fail(RT_EDEVICE, "adaptive mark launch: %s", hipGetErrorString((hipError_t)e));
+        }
+    }
+    if (frame) return rt_resolve_adaptive_async(W, H, d_sums_a, d_sums_b, d_rounds, aparams->first_half, frame, st);
+    return RT_OK;
+}
+
+int rt_render_adaptive(const rt_scene* scene, const rt_params* params, const rt_adaptive_params* aparams,
+                       rt_color* canva, rt_color* albedo, rt_color* normal, int* rounds)
+{
+    int rc, dev;
+    if ((rc = validate_scene(scene))) return rc;
+    if (!params) return fail(RT_EINVAL, "params is NULL");
+    if ((rc = validate_adaptive(aparams))) return rc;
+    rt_params batch = *params;
+    batch.nbRayonParPixel = aparams->first_half;
+    if ((rc = validate_params(&batch))) return rc;
+    if (batch.semantics == RT_SEM_CUDA) return fail(RT_EUNSUPPORTED, "rt_render_adaptive renders RT_SEM_MAIN_C only");
+    const int W = batch.largeur_image, H = batch.hauteur_image;
+    if ((rc = validate_frame(W, H))) return rc;
+    if (!canva) return fail(RT_EINVAL, "adaptive: canva is NULL");
+    if ((rc = first_device(dev))) return rc;
+    std::shared_ptr<rt_device_scene> sc;
+    if ((rc = scene_cache_get(dev, scene, sc))) return rc;
+    StreamLease ps;                  // drained on every return: the caller reads canva next
+    if ((rc = ps.acquire(dev, true))) return rc;
+    DeviceGuard g(dev);
+    const size_t npx = (size_t)W * H, plane = npx * sizeof(rt_color), sums = npx * 9 * sizeof(double);
+    const size_t rbytes = (npx * sizeof(int) + 15) / 16 * 16, ws_bytes = rt_adaptive_workspace_bytes(W, H);
+    rt_color* const dst[3] = {canva, albedo, normal};
+    StreamBuffer dbuf;               // device: the two accumulators, the workspace, the round counts, the planes
+    hipError_t e = ps->reserve_host(3 * plane + rbytes);
+    if (e == hipSuccess) e = dbuf.alloc(2 * sums + ws_bytes + rbytes + 3 * plane, ps->st, dev);
+    if (e != hipSuccess) return fail(RT_ENOMEM, "adaptive buffers: %s", hipGetErrorString(e));
+    char* buf = (char*)dbuf.p;
+    char* ws = buf + 2 * sums;
+    int* d_rounds = (int*)(ws + ws_bytes);
+    char* planes = ws + ws_bytes + rbytes;
+    const rt_frame fr = {(rt_color*)planes, albedo ? (rt_color*)(planes + plane) : nullptr,
+                         normal ? (rt_color*)(planes + 2 * plane) : nullptr, nullptr};
+    if ((rc = rt_adaptive_async(sc.get(), params, aparams, (double*)buf, (double*)(buf + sums), d_rounds, ws, ws_bytes,
+                                &fr, ps->st)))
+        return rc;
+    char* host = (char*)ps->host;
+    for (int pl = 0; pl < 3 && e == hipSuccess; ++pl)
+        if (dst[pl]) e = hipMemcpyAsync(host + pl * plane, planes + pl * plane, plane, hipMemcpyDeviceToHost, ps->st);
+    if (rounds && e == hipSuccess)
+        e = hipMemcpyAsync(host + 3 * plane, d_rounds, npx * sizeof(int), hipMemcpyDeviceToHost, ps->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(ps->st);
+    if (e != hipSuccess) return fail(RT_EDEVICE, "adaptive: %s", hipGetErrorString(e));
+    for (int pl = 0; pl < 3; ++pl)
+        if (dst[pl]) std::memcpy(dst[pl], host + pl * plane, plane);
+    if (rounds) std::memcpy(rounds, host + 3 * plane, npx * sizeof(int));
+    return RT_OK;
+}
+
+}  // extern "C"

@@ -144,11 +144,10 @@ void fill_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling
     fill_kparams(*sc, sc->facts, p, t, g_zero_exit.load() != 0, kp, uni);
 }
 
-// One render or count run of kp as plan_render lays it out, with its stream-
-// ordered scratch (uniform block, the chunk partials of one band).
-// The device's default memory pool keeps freed blocks (release threshold
-// raised once), so repeated launches do not re-map memory.
-int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count)
+// The current device's default memory pool keeps freed blocks (release
+// threshold raised once per device), so repeated launches do not re-map their
+// stream-ordered scratch.
+int keep_pool_memory()
 {
     static std::once_flag pool_once[64];
     int dev = 0;
@@ -162,6 +161,15 @@ int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count)
             }
         });
     }
+    return RT_OK;
+}
+
+// One render or count run of kp as plan_render lays it out, with its stream-
+// ordered scratch (uniform block, the chunk partials of one band).
+int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count)
+{
+    const int rc = keep_pool_memory();
+    if (rc) return rc;
     const RenderPlan plan = plan_render(kp, count);     // kernel, stack and bands, decided once
     double* d_uni = nullptr;
     double* d_part = nullptr;

@@ -69,7 +69,9 @@ int validate_params(const rt_params* p);
 
 // rt_launch_plan.h's fill_kparams on an uploaded scene, with rt_set_zero_throughput_exit's switch;
 // launch_on_stream plans the launch (plan_render) and runs its bands.
+// keep_pool_memory: the launches' stream-ordered scratch stays mapped between calls (once per device).
 void fill_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling* t, KParams& kp, double* uni);
+int keep_pool_memory();
 int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count);
 void free_scene(rt_device_scene* s);
 

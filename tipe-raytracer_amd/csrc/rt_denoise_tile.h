@@ -24,6 +24,13 @@ __device__ __forceinline__ float dist2(const F3 q, const F3 p)
     return (d0 * d0 + d1 * d1) + d2 * d2;
 }
 
+// (0.25f*(D0*D0) + 0.5f*(D1*D1)) + 0.25f*(D2*D2): rt.h's luminance-weighted square
+// (the variance-guided denoiser's v and dl; adaptive sampling's v, rt_adaptive.hip)
+__device__ __forceinline__ float lum2(const float d0, const float d1, const float d2)
+{
+    return (0.25f * (d0 * d0) + 0.5f * (d1 * d1)) + 0.25f * (d2 * d2);
+}
+
 constexpr int kTileX = 64;          // pixels of one row a wave filters: every tap row is one coalesced run
 constexpr int kTileY = 4;           // rows (waves) per block
 constexpr int kTiledRows = kTileY + 4;   // rows a tiled block stages: its own and two tap rows either side

@@ -88,14 +88,21 @@ __device__ __forceinline__ void store3(double* base, long long i, V3 v)
     base[3 * i + 2] = v.z;
 }
 
+// The frame planes of one pixel's sums over S samples (main.c:275-279); albedo,
+// normal and radiance may be null.
+__device__ __forceinline__ void write_planes(double* canva, double* albedo, double* normal, double* radiance,
+                                             long long li, double S, V3 srad, V3 salb, V3 snrm)
+{
+    const double rapport = 1.0 / S;
+    store3(canva, li, v3(resolve(srad.x, rapport), resolve(srad.y, rapport), resolve(srad.z, rapport)));
+    if (albedo) store3(albedo, li, divs(salb, S));
+    if (normal) store3(normal, li, divs(snrm, S));
+    if (radiance) store3(radiance, li, divs(srad, S));
+}
+
 __device__ __forceinline__ void write_pixel(const KParams& kp, long long li, V3 srad, V3 salb, V3 snrm)
 {
-    const double rapport = 1.0 / kp.S;
-    store3(kp.canva, li, v3(resolve(srad.x, rapport), resolve(srad.y, rapport), resolve(srad.z, rapport)));
-    const double S = (double)kp.S;
-    if (kp.albedo) store3(kp.albedo, li, divs(salb, S));
-    if (kp.normal) store3(kp.normal, li, divs(snrm, S));
-    if (kp.radiance) store3(kp.radiance, li, divs(srad, S));
+    write_planes(kp.canva, kp.albedo, kp.normal, kp.radiance, li, (double)kp.S, srad, salb, snrm);
 }
 
 // Primary ray of sample st (main.c:258-270; camera.h:42-55 get_ray).

@@ -211,4 +211,42 @@ int launch_vdenoise(int W, int H, const double* sums_a, const double* sums_b, in
                     float sigma_luminance, float sigma_normal, float sigma_albedo, float* workspace, double* canva,
                     double* albedo, double* normal, double* radiance, void* stream);
 
+// launchers (rt_adaptive.hip): adaptive sampling (rt.h "adaptive sampling").
+// What a list launch needs besides KParams, as the render kernel's second
+// by-value argument (KParams stays as it is): one band [e0, e1) of the entries.
+struct ListArgs {
+    const unsigned* list;    // global pixel indices j*W+i, ascending
+    const unsigned* count;   // device word: entries of the list (the kernel clamps it to e1)
+    double* partial;         // chunks > 1: [chunks][stride][9], indexed by entry - e0
+    unsigned e0, e1;         // this launch's entries; e1 <= list_cap
+    unsigned stride;         // entries of one chunk's plane of partial (the band size)
+};
+int launch_render_list(const KParams& kp, const RenderPlan& plan, const ListArgs& la, void* stream);
+// One selection pass (rt_adaptive_select_async) or one marking of the active
+// pixels' round counts, as their kernels' by-value argument.
+struct AdaptiveSelect {
+    int W, H;
+    unsigned npx;            // W * H <= 2^30
+    int all;                 // round 0: every pixel is active and the incoming list is not read
+    const double* sums_a;
+    const double* sums_b;
+    double rap;              // 1.0 / n_half
+    float tolerance;
+    int round;
+    unsigned* list;          // in: the active pixels (unless all); out: those that go on
+    unsigned* count;         // in / out: entries of list
+    int* rounds;
+    float* v;                // workspace planes: v and y per pixel (kept between calls),
+    float* y;
+    unsigned* keep;          //   per active entry its pixel or "settled" (padded to whole blocks of 256),
+    unsigned* counts;        //   kept entries per block of 256, then their exclusive scan,
+    unsigned* n_in;          //   and the incoming count (the scatter reads it after *count changed)
+};
+unsigned adaptive_blocks(long long npx);                // blocks of 256 entries: the length of counts
+int launch_adaptive_select(const AdaptiveSelect& s, void* stream);
+int launch_adaptive_mark(const AdaptiveSelect& s, int value, void* stream);
+int launch_adaptive_resolve(long long npx, const double* sums_a, const double* sums_b, const int* rounds,
+                            int first_half, double* canva, double* albedo, double* normal, double* radiance,
+                            void* stream);
+
 }  // namespace rt

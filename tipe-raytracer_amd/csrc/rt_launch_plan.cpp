@@ -195,4 +195,31 @@ RenderPlan plan_render(const KParams& kp, bool count)
     return pl;
 }
 
+// Entries per band of a chunked list launch: the whole list (list_cap in whole
+// blocks of 256 entries) when its partials, chunks x 72 bytes per entry, fit
+// kListPartialBudget, else as many whole blocks as fit.  The count is a device
+// word, so every band up to list_cap is launched and each launch ends in a tail
+// of half-idle CUs: few large bands cost less than many small ones
+// (profiles/adaptive/README.md, "Band size").  512 MiB is what a 1200x900 frame
+// may take at P = 32: 232 960 entries, five bands; a small frame takes what its
+// own pixels need.  RT_LIST_BAND (entries; tests, experiments) is read on every
+// launch, so a test can give a small list several bands.
+constexpr size_t kListPartialBudget = (size_t)512 << 20;
+
+ListPlan plan_list(int chunks, unsigned list_cap)
+{
+    ListPlan pl = {list_cap, 0};
+    if (chunks <= 1) return pl;
+    const size_t per_entry = (size_t)chunks * 9 * sizeof(double);
+    size_t band = std::max<size_t>(256, kListPartialBudget / per_entry / 256 * 256);
+    if (const char* e = std::getenv("RT_LIST_BAND")) {
+        const long long v = std::atoll(e);
+        if (v > 0) band = std::min(band, ((size_t)std::min<long long>(v, 1ll << 30) + 255) / 256 * 256);
+    }
+    band = std::min(band, ((size_t)list_cap + 255) / 256 * 256);
+    pl.band = (unsigned)band;
+    pl.partial_bytes = band * per_entry;
+    return pl;
+}
+
 }  // namespace rt

@@ -102,4 +102,13 @@ struct RenderPlan {
 };
 RenderPlan plan_render(const KParams& kp, bool count);
 
+// The entry bands of a list launch (rt_accumulate_list_async) of up to list_cap
+// entries with `chunks` sample slices; launch_render_list (rt_adaptive.hip) runs
+// one band.
+struct ListPlan {
+    unsigned band;           // entries per launch; the partials are per band (chunks 1: one band, no partials)
+    size_t partial_bytes;    // chunk partials of one band, [chunks][band][9] doubles (0: none)
+};
+ListPlan plan_list(int chunks, unsigned list_cap);
+
 }  // namespace rt

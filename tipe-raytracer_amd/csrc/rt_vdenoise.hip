@@ -18,12 +18,6 @@ namespace rt {
 
 namespace {
 
-// (0.25f*(D0*D0) + 0.5f*(D1*D1)) + 0.25f*(D2*D2): rt.h's luminance-weighted square
-__device__ __forceinline__ float lum2(const float d0, const float d1, const float d2)
-{
-    return (0.25f * (d0 * d0) + 0.5f * (d1 * d1)) + 0.25f * (d2 * d2);
-}
-
 // Grid-stride kernels: 2048 blocks of 256 threads fill the 256 CUs (8 blocks each).
 unsigned grid_1d(long long n) { return (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048); }
 

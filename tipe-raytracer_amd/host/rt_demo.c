@@ -6,13 +6,16 @@
  *
  *   rt_demo [-w W] [-s spp] [-b nbRebondMax] [-ao AO_intensity] [-o out.ppm]
  *           [-obj file.obj -mtl file.mtl [-move x y z]] [-devices N]
- *           [-denoise [iterations]] [-vdenoise [iterations]]
+ *           [-denoise [iterations]] [-vdenoise [iterations]] [-adaptive TOL]
  *
  * -denoise installs the library's built-in a-trous filter (rt_denoise_atrous;
  * not OIDN, and biased: meant for low-spp frames) as the denoiser hook before
  * the render, with `iterations` passes (default 4; more for larger frames).
  * -vdenoise renders through rt_render_vdenoised instead: the variance-guided
  * denoiser over the frame's two sample halves (spp must be even; one device).
+ * -adaptive renders through rt_render_adaptive with tolerance TOL (the other
+ * parameters at their defaults; -s is ignored; one device) and also prints the
+ * mean samples per pixel and the share of pixels per round count.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -33,6 +36,9 @@ int main(int argc, char** argv)
     int vdenoise = 0;
     rt_vdenoise_params vdn;
     rt_vdenoise_params_init(&vdn);
+    int adaptive = 0;
+    rt_adaptive_params adp;
+    rt_adaptive_params_init(&adp);
     double AO = 2.5, mx = 0, my = 0, mz = 0;
     const char *out = "render.ppm", *obj = NULL, *mtl = NULL;
     for (int i = 1; i < argc; i++) {
@@ -50,6 +56,9 @@ int main(int argc, char** argv)
         } else if (!strcmp(argv[i], "-vdenoise")) {
             vdenoise = 1;
             if (i + 1 < argc && argv[i + 1][0] != '-') vdn.iterations = atoi(argv[++i]);
+        } else if (!strcmp(argv[i], "-adaptive") && i + 1 < argc) {
+            adaptive = 1;
+            adp.tolerance = (float)atof(argv[++i]);
         } else if (!strcmp(argv[i], "-move") && i + 3 < argc) {
             mx = atof(argv[++i]);
             my = atof(argv[++i]);
@@ -57,7 +66,7 @@ int main(int argc, char** argv)
         } else {
             fprintf(stderr, "usage: %s [-w W] [-s spp] [-b bounces] [-ao I] [-o out.ppm] "
                             "[-obj f.obj -mtl f.mtl [-move x y z]] [-devices N] [-denoise [iterations]] "
-                            "[-vdenoise [iterations]]\n",
+                            "[-vdenoise [iterations]] [-adaptive TOL]\n",
                     argv[0]);
             return 2;
         }
@@ -126,15 +135,35 @@ int main(int argc, char** argv)
     rt_color* canva = (rt_color*)calloc(n, sizeof(rt_color));
     rt_color* albedo = (rt_color*)calloc(n, sizeof(rt_color));
     rt_color* normal = (rt_color*)calloc(n, sizeof(rt_color));
+    int* rounds = adaptive ? (int*)calloc(n, sizeof(int)) : NULL;
     struct timeval t0, t1;
     gettimeofday(&t0, NULL);
-    int rc = vdenoise ? rt_render_vdenoised(&scene, &p, &vdn, canva, albedo, normal)
-                      : rt_render_rows(&scene, &p, H - 1, 0, canva, albedo, normal);
+    int rc = adaptive   ? rt_render_adaptive(&scene, &p, &adp, canva, albedo, normal, rounds)
+             : vdenoise ? rt_render_vdenoised(&scene, &p, &vdn, canva, albedo, normal)
+                        : rt_render_rows(&scene, &p, H - 1, 0, canva, albedo, normal);
     gettimeofday(&t1, NULL);
-    if (rc) { fprintf(stderr, "%s: %s\n", vdenoise ? "rt_render_vdenoised" : "rt_render_rows", rt_last_error()); return 1; }
+    if (rc) {
+        fprintf(stderr, "%s: %s\n", adaptive ? "rt_render_adaptive" : vdenoise ? "rt_render_vdenoised" : "rt_render_rows",
+                rt_last_error());
+        return 1;
+    }
     double dt = (t1.tv_sec - t0.tv_sec) + 1e-6 * (t1.tv_usec - t0.tv_usec);
-    fprintf(stderr, "%dx%d, %d spp, %d bounces: %.3f s, %.1f Msamples/s (end-to-end)\n", W, H, spp, bounces, dt,
-            (double)n * spp / dt / 1e6);
+    if (adaptive) {      /* samples of a pixel with k rounds: 2 * first_half * 2^(k-1) */
+        double total = 0, share[17] = {0};
+        for (size_t i = 0; i < n; i++) {
+            int k = rounds[i] < 1 ? 1 : rounds[i] > 16 ? 16 : rounds[i];
+            total += (double)adp.first_half * (double)(1 << k);
+            share[k] += 1.0 / (double)n;
+        }
+        fprintf(stderr, "adaptive, tolerance %g: %.2f samples per pixel on average; pixels per round count:", adp.tolerance,
+                total / (double)n);
+        for (int k = 1; k <= adp.max_rounds; k++) fprintf(stderr, " %d: %.1f %%", k, 100.0 * share[k]);
+        fprintf(stderr, "\n%dx%d, %d bounces: %.3f s, %.1f Msamples/s (end-to-end)\n", W, H, bounces, dt, total / dt / 1e6);
+        free(rounds);
+    } else {
+        fprintf(stderr, "%dx%d, %d spp, %d bounces: %.3f s, %.1f Msamples/s (end-to-end)\n", W, H, spp, bounces, dt,
+                (double)n * spp / dt / 1e6);
+    }
     rc = rt_host_write_ppm(out, canva, W, H);
     free(canva);
     free(albedo);

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from .types import (Vec3, Ray, Material, Sphere, UV, Triangle, Camera, ThreadData, Scene,  # noqa: F401
-                    Params, Tiling, Frame, DenoiseParams, VDenoiseParams, RT_OK, RT_EINVAL, RT_EDEVICE, RT_ENOMEM, RT_EUNSUPPORTED,
+                    Params, Tiling, Frame, DenoiseParams, VDenoiseParams, AdaptiveParams, RT_OK, RT_EINVAL, RT_EDEVICE, RT_ENOMEM, RT_EUNSUPPORTED,
                     RT_RNG_PHILOX, RT_RNG_GLIBC, RT_NCOUNTERS, COUNTER_NAMES, RT_SPP_CHUNKS_AUTO,
                     RT_SPP_CHUNKS_DEFAULT)
 
@@ -105,6 +105,22 @@ def lib():
                                             C.c_void_p, C.c_size_t, P(Frame), C.c_void_p]
             L.rt_render_vdenoised.argtypes = [P(Scene), P(Params), P(VDenoiseParams), C.c_void_p, C.c_void_p,
                                               C.c_void_p]
+        if hasattr(L, "rt_adaptive_async"):      # (added to ABI 5 as well)
+            L.rt_accumulate_list_async.argtypes = [C.c_void_p, P(Params), C.c_longlong, C.c_void_p, C.c_void_p,
+                                                   C.c_uint, C.c_void_p, C.c_void_p]
+            L.rt_adaptive_workspace_bytes.argtypes = [C.c_int, C.c_int]
+            L.rt_adaptive_workspace_bytes.restype = C.c_size_t
+            L.rt_adaptive_select_async.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
+                                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_size_t, C.c_void_p]
+            L.rt_adaptive_params_init.argtypes = [P(AdaptiveParams)]
+            L.rt_adaptive_params_init.restype = None
+            L.rt_adaptive_async.argtypes = [C.c_void_p, P(Params), P(AdaptiveParams), C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_size_t, P(Frame), C.c_void_p]
+            L.rt_resolve_adaptive_async.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                    P(Frame), C.c_void_p]
+            L.rt_render_adaptive.argtypes = [P(Scene), P(Params), P(AdaptiveParams), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -119,7 +135,9 @@ EXPORTED_SYMBOLS = ["rt_params_init", "rt_init", "rt_shutdown", "rt_last_error",
                     "rt_last_render_kernel", "rt_denoise_params_init", "rt_denoise_workspace_bytes",
                     "rt_denoise_async", "rt_denoise_host", "rt_denoise_atrous", "rt_set_denoise_params",
                     "rt_vdenoise_params_init", "rt_vdenoise_workspace_bytes", "rt_vdenoise_async",
-                    "rt_render_vdenoised"]
+                    "rt_render_vdenoised", "rt_accumulate_list_async", "rt_adaptive_select_async",
+                    "rt_adaptive_workspace_bytes", "rt_adaptive_params_init", "rt_adaptive_async",
+                    "rt_resolve_adaptive_async", "rt_render_adaptive"]
 
 # rt_denoise_fn (rt.h): denoiser()'s signature, denoiser.h:31
 DENOISE_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p, Camera, C.c_void_p, C.c_void_p)
@@ -246,6 +264,60 @@ def render_vdenoised(scene, params, vparams=None, albedo=True, normal=True):
                                     alb.ctypes.data if alb is not None else None,
                                     nrm.ctypes.data if nrm is not None else None))
     return canva, alb, nrm
+
+
+def adaptive_params(first_half=None, max_rounds=None, tolerance=None):
+    """rt_adaptive_params_init's defaults (8, 5, 1/64) with the given fields replaced."""
+    p = AdaptiveParams()
+    lib().rt_adaptive_params_init(C.byref(p))
+    for name, v in (("first_half", first_half), ("max_rounds", max_rounds), ("tolerance", tolerance)):
+        if v is not None:
+            setattr(p, name, v)
+    return p
+
+
+def accumulate_list_async(dscene, params, sample_offset, list_ptr, count_ptr, list_cap, sums_ptr, stream=None):
+    """rt_accumulate_list_async: add samples [offset, offset + S) of the listed pixels into d_sums."""
+    check(lib().rt_accumulate_list_async(dscene.handle, C.byref(params), sample_offset, list_ptr, count_ptr, list_cap,
+                                         sums_ptr, stream))
+
+
+def adaptive_select_async(W, H, sums_a_ptr, sums_b_ptr, n_half, tolerance, round, list_ptr, count_ptr, rounds_ptr,
+                          workspace_ptr, workspace_bytes, stream=None):
+    """rt_adaptive_select_async: the settled test and the compaction of the pixels that go on."""
+    check(lib().rt_adaptive_select_async(W, H, sums_a_ptr, sums_b_ptr, n_half, tolerance, round, list_ptr, count_ptr,
+                                         rounds_ptr, workspace_ptr, workspace_bytes, stream))
+
+
+def adaptive_async(dscene, params, aparams, sums_a_ptr, sums_b_ptr, rounds_ptr, workspace_ptr, workspace_bytes,
+                   canva_ptr=None, albedo_ptr=None, normal_ptr=None, radiance_ptr=None, stream=None):
+    """rt_adaptive_async: the adaptive loop on two device accumulators; the
+    frame planes are resolved when canva_ptr is given."""
+    fr = Frame(canva_ptr, albedo_ptr, normal_ptr, radiance_ptr) if canva_ptr else None
+    check(lib().rt_adaptive_async(dscene.handle, C.byref(params), C.byref(aparams), sums_a_ptr, sums_b_ptr,
+                                  rounds_ptr, workspace_ptr, workspace_bytes, C.byref(fr) if fr else None, stream))
+
+
+def resolve_adaptive_async(W, H, sums_a_ptr, sums_b_ptr, rounds_ptr, first_half, canva_ptr, albedo_ptr=None,
+                           normal_ptr=None, radiance_ptr=None, stream=None):
+    """rt_resolve_adaptive_async: the frame planes of A + B with each pixel's own sample count."""
+    fr = Frame(canva_ptr, albedo_ptr, normal_ptr, radiance_ptr)
+    check(lib().rt_resolve_adaptive_async(W, H, sums_a_ptr, sums_b_ptr, rounds_ptr, first_half, C.byref(fr), stream))
+
+
+def render_adaptive(scene, params, aparams=None, albedo=True, normal=True):
+    """rt_render_adaptive into fresh arrays: (canva, albedo, normal, rounds),
+    three (H, W, 3) float64 planes and the (H, W) int32 round counts."""
+    W, H = params.largeur_image, params.hauteur_image
+    canva = np.zeros((H, W, 3))
+    alb = np.zeros((H, W, 3)) if albedo else None
+    nrm = np.zeros((H, W, 3)) if normal else None
+    rounds = np.zeros((H, W), dtype=np.int32)
+    ap = aparams if aparams is not None else adaptive_params()
+    check(lib().rt_render_adaptive(C.byref(scene), C.byref(params), C.byref(ap), canva.ctypes.data,
+                                   alb.ctypes.data if alb is not None else None,
+                                   nrm.ctypes.data if nrm is not None else None, rounds.ctypes.data))
+    return canva, alb, nrm, rounds
 
 
 def last_gather_transport():

@@ -157,5 +157,10 @@ class VDenoiseParams(C.Structure):
                 ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float)]
 
 
+class AdaptiveParams(C.Structure):
+    """rt.h rt_adaptive_params: adaptive sampling's schedule and tolerance."""
+    _fields_ = [("first_half", C.c_int), ("max_rounds", C.c_int), ("tolerance", C.c_float)]
+
+
 assert C.sizeof(Vec3) == 24 and C.sizeof(Material) == 80 and C.sizeof(Sphere) == 112
 assert C.sizeof(Triangle) == 200 and C.sizeof(Camera) == 96 and C.sizeof(ThreadData) == 248

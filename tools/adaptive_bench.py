@@ -1,0 +1,175 @@
+#!/usr/bin/env python3
+"""Time adaptive sampling (rt_adaptive_async) against uniform renders of the same scene.
+
+    tools/adaptive_bench.py [--scenes box,nature] [--size 1200x900] [--reps 5] [--warmup 1] [--label TAG]
+                            [--first-half 8] [--max-rounds 5] [--tolerance 0.015625]
+
+Per scene, JSON lines (device-event times, every repetition listed so the spread shows):
+  adaptive        rt_adaptive_async at the given parameters (A, B, d_rounds and the frame planes), its total
+                  samples, the mean per pixel and the share of pixels per round count;
+  uniform_max     two rt_accumulate_async calls + rt_resolve_async at the adaptive schedule's maximum count;
+  uniform_mean    the same at the even count nearest the adaptive frame's mean;
+  round           for each round, host-driven through the public calls (accumulate, select, one read of the
+                  count): the list size and, for rounds >= 1, the list kernel's samples per second next to the
+                  dense fixed-grid kernel's on the same batch size over the whole frame (rt_accumulate_async:
+                  the parent's code, the yardstick); round 0 also times the list kernel on a list of every
+                  pixel, which separates the cost of the entry map from that of the pixels a list keeps.
+The box is the README scene (spheres only), nature the reference's RTX_MAP/nature mesh under its own camera."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tipe-raytracer_amd"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", default="box,nature")
+    ap.add_argument("--size", default="1200x900")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--label", default="")
+    ap.add_argument("--first-half", type=int, default=None)
+    ap.add_argument("--max-rounds", type=int, default=None)
+    ap.add_argument("--tolerance", type=float, default=None)
+    args = ap.parse_args()
+    import torch
+    import tipe_rt
+    from tipe_rt import scenes
+    if not torch.cuda.is_available():
+        sys.exit("adaptive_bench: needs a GPU (no CPU fallback)")
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    W, H = (int(v) for v in args.size.split("x"))
+    npx = W * H
+    adp = tipe_rt.adaptive_params(first_half=args.first_half, max_rounds=args.max_rounds, tolerance=args.tolerance)
+    fh, R = adp.first_half, adp.max_rounds
+    band = tipe_rt.band_tiling(0, H - 1)
+
+    def timed(call, reps=args.reps, warmup=args.warmup):
+        """Milliseconds of each repetition."""
+        for _ in range(warmup):
+            call()
+        torch.cuda.synchronize()
+        out = []
+        for _ in range(reps):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            call()
+            t1.record()
+            torch.cuda.synchronize()
+            out.append(round(t0.elapsed_time(t1), 3))
+        return out
+
+    def emit(**kw):
+        print(json.dumps(dict(label=args.label, W=W, H=H, first_half=fh, max_rounds=R,
+                              tolerance=float(adp.tolerance), **kw)), flush=True)
+
+    for name in args.scenes.split(","):
+        if name == "nature":
+            tris, qm, mats, tw, th, nm = scenes.nature_mesh()
+            scene = tipe_rt.make_scene(scenes.main_spheres(), tris, qm, mats, tw, th, nm)
+            spec, bounces = scenes.NATURE_CAMERA, 10
+        else:
+            scene = tipe_rt.make_scene(scenes.cornell_spheres())
+            spec, bounces = scenes.README_CAMERA, 6
+        cam = tipe_rt.init_camera(**{k: spec[k] for k in ("origin", "target", "up", "vfov", "ratio")})
+        p = tipe_rt.make_params(W, H, 1, bounces, cam, focus=3.0, chunks=tipe_rt.RT_SPP_CHUNKS_AUTO)
+        ds = tipe_rt.DeviceScene(scene, 0)
+        acc = torch.zeros((2, H, W, 9), dtype=torch.float64, device=dev)
+        rounds = torch.zeros((H, W), dtype=torch.int32, device=dev)
+        planes = torch.zeros((3, H, W, 3), dtype=torch.float64, device=dev)
+        nbytes = tipe_rt.lib().rt_adaptive_workspace_bytes(W, H)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+        def with_spp(n):
+            q = type(p).from_buffer_copy(p)
+            q.nbRayonParPixel = n
+            return q
+
+        def adaptive():
+            tipe_rt.adaptive_async(ds, p, adp, acc[0].data_ptr(), acc[1].data_ptr(), rounds.data_ptr(), ws.data_ptr(),
+                                   nbytes, planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(), stream=st)
+
+        ms = timed(adaptive)
+        k = rounds.cpu().numpy()
+        counts = 2.0 * fh * 2.0 ** (k - 1)
+        mean = float(counts.mean())
+        emit(scene=name, what="adaptive", ms=ms, total_samples=float(counts.sum()), mean_spp=round(mean, 3),
+             share_per_round=[round(float((k == r).mean()), 4) for r in range(1, R + 1)])
+
+        def uniform(half):
+            def call():
+                acc.zero_()
+                for j in range(2):
+                    tipe_rt.accumulate_async(ds, with_spp(half), j * half, band, acc[j].data_ptr(), st)
+                acc[0].add_(acc[1])
+                tipe_rt.resolve_async(acc[0].data_ptr(), p, 2 * half, band, planes[0].data_ptr(), planes[1].data_ptr(),
+                                      planes[2].data_ptr(), stream=st)
+            return call
+
+        half_max = fh << (R - 1)
+        half_mean = max(1, int(round(mean / 2.0)))
+        emit(scene=name, what="uniform_max", spp=2 * half_max, ms=timed(uniform(half_max)),
+             total_samples=2.0 * half_max * npx)
+        emit(scene=name, what="uniform_mean", spp=2 * half_mean, ms=timed(uniform(half_mean)),
+             total_samples=2.0 * half_mean * npx)
+
+        # round by round through the public calls
+        lst = torch.zeros(npx, dtype=torch.int32, device=dev)
+        cnt = torch.zeros(4, dtype=torch.int32, device=dev)
+        acc.zero_()
+        scratch = torch.zeros((H, W, 9), dtype=torch.float64, device=dev)
+        n_list = npx
+        for r in range(R):
+            n_r = fh << r
+            b, o = (n_r, 0) if r == 0 else (n_r // 2, n_r)
+            pb = with_spp(b)
+
+            def dense():
+                tipe_rt.accumulate_async(ds, pb, o, band, scratch.data_ptr(), st)
+
+            dense_ms = timed(dense)
+            line = dict(scene=name, what="round", round=r, batch=b, list_size=n_list, dense_ms=dense_ms,
+                        dense_msamples_per_s=round(npx * b / (float(np.median(dense_ms)) * 1e-3) / 1e6, 1))
+            if r == 0:
+                # the list kernel on every pixel against the dense kernel: what the entry map costs by itself
+                every = torch.arange(npx, dtype=torch.int32, device=dev)
+                n_every = torch.tensor([npx, 0, 0, 0], dtype=torch.int32, device=dev)
+
+                def full_list():
+                    tipe_rt.accumulate_list_async(ds, pb, o, every.data_ptr(), n_every.data_ptr(), npx,
+                                                  scratch.data_ptr(), st)
+
+                full_ms = timed(full_list)
+                line.update(full_list_ms=full_ms, full_list_msamples_per_s=round(
+                    npx * b / (float(np.median(full_ms)) * 1e-3) / 1e6, 1))
+                for j in range(2):
+                    tipe_rt.accumulate_async(ds, pb, o + j * b, band, acc[j].data_ptr(), st)
+            else:
+                def listed():
+                    tipe_rt.accumulate_list_async(ds, pb, o, lst.data_ptr(), cnt.data_ptr(), npx, scratch.data_ptr(),
+                                                  st)
+
+                list_ms = timed(listed)
+                line.update(list_ms=list_ms, list_msamples_per_s=round(
+                    n_list * b / (float(np.median(list_ms)) * 1e-3) / 1e6, 1) if n_list else None)
+                for j in range(2):
+                    tipe_rt.accumulate_list_async(ds, pb, o + j * b, lst.data_ptr(), cnt.data_ptr(), npx,
+                                                  acc[j].data_ptr(), st)
+            emit(**line)
+            if r < R - 1:
+                tipe_rt.adaptive_select_async(W, H, acc[0].data_ptr(), acc[1].data_ptr(), n_r, float(adp.tolerance), r,
+                                              lst.data_ptr(), cnt.data_ptr(), rounds.data_ptr(), ws.data_ptr(), nbytes,
+                                              stream=st)
+                torch.cuda.synchronize()
+                n_list = int(cnt[0])
+        ds.close()
+
+
+if __name__ == "__main__":
+    main()
