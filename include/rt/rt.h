@@ -48,7 +48,10 @@ extern "C" {
  *    rt_vdenoise_workspace_bytes, rt_vdenoise_async, rt_render_vdenoised);
  *    adaptive sampling (rt_accumulate_list_async, rt_adaptive_select_async,
  *    rt_adaptive_workspace_bytes, rt_adaptive_params, rt_adaptive_params_init,
- *    rt_adaptive_async, rt_resolve_adaptive_async, rt_render_adaptive).
+ *    rt_adaptive_async, rt_resolve_adaptive_async, rt_render_adaptive);
+ *    the variance-guided denoiser with each pixel's own sample count, which
+ *    filters an adaptive result (rt_vdenoise_adaptive_async,
+ *    rt_render_adaptive_vdenoised).
  * A caller compares rt_abi_version() with the RT_ABI_VERSION it was built
  * against before passing rt_params or counter arrays.                   */
 #define RT_ABI_VERSION 5
@@ -713,11 +716,55 @@ int rt_resolve_adaptive_async(int W, int H, const double* d_sums_a, const double
  * scene, pooled stream, pinned staging; canva, albedo / normal and rounds
  * (W*H ints) when not NULL are written only on success.
  *
- * Out of scope: rt_vdenoise_async takes one spp_half for the frame, so it
- * cannot yet filter an adaptive result; cyclic tiles and multi-device
- * rendering; RT_SEM_CUDA; running the list on the task-queue kernel. */
+ * Out of scope: cyclic tiles and multi-device rendering; RT_SEM_CUDA; running
+ * the list on the task-queue kernel. */
 int rt_render_adaptive(const rt_scene* scene, const rt_params* params, const rt_adaptive_params* aparams,
                        rt_color* canva, rt_color* albedo, rt_color* normal, int* rounds);
+
+/* ---- variance-guided denoiser with per-pixel sample counts ------------------ */
+/* The variance-guided denoiser above on an adaptive result: A, B and d_rounds
+ * exactly as rt_adaptive_async leaves them (meant to be enqueued right behind
+ * that call on the same stream, with frame = NULL there).  Everything is the
+ * text of "variance-guided denoiser" except the sample count, which is each
+ * pixel's own.  For pixel p:
+ *   k   = min(max(d_rounds[p], 1), 32)       (rt_resolve_adaptive_async's clamp)
+ *   n_p = first_half * 2^(k-1)               (a 64-bit integer; samples per accumulator)
+ * and n becomes n_p in two places:
+ *   - means and variance:  rap = 1.0 / (double)n_p, per pixel; mX, c, a, nn, d
+ *     and v as written there;
+ *   - finish: albedo and normal receive (A + B) * (1.0 / (2.0 * (double)n_p)),
+ *     that quotient first.
+ * The passes, canva and radiance are unchanged: after the means the filter
+ * does not know the counts.  A float32 restatement equals the GPU bit for bit,
+ * and with d_rounds == k everywhere the result is rt_vdenoise_async's at
+ * spp_half = first_half * 2^(k-1).  With iterations = 0 the unfiltered float
+ * mean is resolved, as there.
+ *
+ * workspace: as rt_vdenoise_async's, rt_vdenoise_workspace_bytes(W, H) bytes.
+ * Allocates and synchronises nothing; the accumulators and d_rounds are
+ * read-only; d_rounds values are device data and are not validated beyond the
+ * clamp.  RT_EINVAL before any device work for everything rt_vdenoise_async
+ * refuses, with first_half < 1 in spp_half's place, and for a NULL d_rounds.
+ *
+ * A known limit: the variance estimate of a pixel that stopped early is biased
+ * low.  A pixel settles when its two halves agree, and with few samples they
+ * sometimes agree by chance; such a pixel carries a small v, so the filter
+ * leaves it alone although it is noisy.  At first_half = 8 (the default) a
+ * filtered adaptive frame is as close to the truth as a filtered uniform frame
+ * of the same budget; at first_half = 2 it is measurably worse.
+ * No correction is applied. */
+int rt_vdenoise_adaptive_async(int W, int H, const double* d_sums_a, const double* d_sums_b, const int* d_rounds,
+                               int first_half, const rt_vdenoise_params* params, void* workspace,
+                               size_t workspace_bytes, const rt_frame* out, void* hip_stream);
+/* rt_render_adaptive with the filter in place of rt_resolve_adaptive_async:
+ * the same loop on rt_init's first device (cached scene, pooled stream, pinned
+ * staging), then rt_vdenoise_adaptive_async on the same stream.  vparams is
+ * validated as rt_vdenoise_async's, before any device work.  canva, and
+ * albedo / normal / rounds when not NULL, are written only on success;
+ * rounds equal rt_render_adaptive's. */
+int rt_render_adaptive_vdenoised(const rt_scene* scene, const rt_params* params, const rt_adaptive_params* aparams,
+                                 const rt_vdenoise_params* vparams, rt_color* canva, rt_color* albedo,
+                                 rt_color* normal, int* rounds);
 
 /* Device-math self test: evaluates one device primitive on n host inputs
  * (synchronous, device 0).  op: 0 acos, 1 sinf, 2 cosf, 3 pow(x, y),

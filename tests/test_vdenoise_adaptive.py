@@ -1,0 +1,352 @@
+"""The variance-guided denoiser on an adaptive result (rt.h "variance-guided
+denoiser with per-pixel sample counts"): rt_vdenoise_adaptive_async, which
+reads each pixel's sample count from rt_adaptive_async's d_rounds, and
+rt_render_adaptive_vdenoised, the whole frame into host arrays.
+
+The references are the float32 restatement in vdenoise_adaptive_support.py
+(written from rt.h's text), the existing uniform filter (rt_vdenoise_async,
+vdenoise_support.restate) where the counts are equal, and for quality the
+existing uniform path rt_render_vdenoised; never the new code.  Comparisons
+are bit for bit on uint64 views unless a test says otherwise."""
+import ctypes as C
+import functools
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers
+import tipe_rt
+import vdenoise_support as uniform
+from adaptive_support import u64
+from tipe_rt import types as T
+from vdenoise_adaptive_support import case, counts, device_filter, enqueue, kwargs_of, mixed_rounds, restate, sums
+from vdenoise_support import DEFAULTS, PLANES, assert_planes, params_of
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = {"rt_vdenoise_adaptive_async", "rt_render_adaptive_vdenoised"}
+
+
+# ---- without a GPU ------------------------------------------------------------
+
+def test_entry_points_are_exported_and_bound():
+    out = subprocess.run(["nm", "-D", "--defined-only", tipe_rt.LIB_PATH], capture_output=True, text=True,
+                         check=True).stdout
+    syms = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert NEW <= syms and NEW <= set(tipe_rt.EXPORTED_SYMBOLS)
+    L = tipe_rt.lib()
+    assert len(L.rt_vdenoise_adaptive_async.argtypes) == 11 and len(L.rt_render_adaptive_vdenoised.argtypes) == 8
+    assert callable(tipe_rt.vdenoise_adaptive_async) and callable(tipe_rt.render_adaptive_vdenoised)
+    assert L.rt_abi_version() == 5                      # additions to 5: detected by symbol
+
+
+def test_validation_fails_before_any_device_work():
+    """Everything rt_vdenoise_async refuses, a NULL d_rounds and first_half < 1:
+    RT_EINVAL with a message; the pointers are never dereferenced (they are not
+    device memory)."""
+    L = tipe_rt.lib()
+    W, H = 8, 6
+    fake = 0x10000
+    nbytes = L.rt_vdenoise_workspace_bytes(W, H)
+    good = params_of()
+    frame = T.Frame(fake, fake, fake, fake)
+
+    def refused(rc):
+        assert rc == T.RT_EINVAL
+        assert L.rt_last_error()
+
+    def run(W=W, H=H, a=fake, b=fake, rounds=fake, fh=4, params=good, ws=fake, nbytes=nbytes, out=frame):
+        return L.rt_vdenoise_adaptive_async(W, H, a, b, rounds, fh, None if params is None else C.byref(params), ws,
+                                            nbytes, None if out is None else C.byref(out), None)
+
+    refused(run(W=0))
+    refused(run(H=0))
+    refused(run(W=-3))
+    refused(run(W=32769, H=32768, nbytes=1 << 62))            # above 2^30 pixels, nothing else to refuse it for
+    refused(run(a=None))
+    refused(run(b=None))
+    refused(run(rounds=None))
+    refused(run(params=None))
+    refused(run(out=None))
+    refused(run(out=T.Frame(None, fake, fake, fake)))
+    refused(run(fh=0))
+    refused(run(fh=-2))
+    refused(run(ws=None))
+    refused(run(nbytes=nbytes - 1))
+    refused(run(nbytes=0))
+    refused(run(ws=fake + 4))                                  # misaligned: 16 bytes are required
+    refused(run(ws=fake + 8))
+    for it in (-1, 9):
+        refused(run(params=params_of(iterations=it)))
+    bad_sigmas = (math.nan, math.inf, -math.inf, 0.0, -1.0, 2.0 ** -9, np.nextafter(np.float32(2.0 ** -8), np.float32(0)),
+                  np.nextafter(np.float32(2.0 ** 8), np.float32(1e9)), 1e30)
+    for field in ("sigma_luminance", "sigma_normal", "sigma_albedo"):
+        for v in bad_sigmas:
+            refused(run(params=params_of(**{field: float(v)})))
+    # the host path: rt_render_adaptive's refusals and the filter's parameters; nothing is written
+    bundle = helpers.cornell()
+    canva, alb, nrm = (np.full((H, W, 3), -3.0) for _ in range(3))
+    rounds = np.full((H, W), -3, dtype=np.int32)
+    ap_good = tipe_rt.adaptive_params()
+
+    def host(ap=ap_good, vp=good, canva_ptr=canva.ctypes.data, scene=bundle.scene, p=helpers.params(W, H, 1, 3)):
+        return L.rt_render_adaptive_vdenoised(None if scene is None else C.byref(scene), C.byref(p),
+                                              None if ap is None else C.byref(ap), None if vp is None else C.byref(vp),
+                                              canva_ptr, alb.ctypes.data, nrm.ctypes.data, rounds.ctypes.data)
+
+    refused(host(vp=None))
+    refused(host(vp=params_of(iterations=9)))
+    refused(host(vp=params_of(sigma_luminance=math.nan)))
+    refused(host(ap=None))
+    refused(host(ap=tipe_rt.adaptive_params(first_half=0)))
+    refused(host(ap=tipe_rt.adaptive_params(tolerance=2.0)))
+    refused(host(canva_ptr=None))
+    refused(host(scene=None))
+    assert host(p=helpers.params(W, H, 1, 3, semantics=1)) == T.RT_EUNSUPPORTED
+    assert (canva == -3).all() and (alb == -3).all() and (nrm == -3).all() and (rounds == -3).all()
+
+
+UNIFORM_CASES = [(1, 1), (5, 3), (8, 5)]
+
+
+@pytest.mark.parametrize("first_half,k", UNIFORM_CASES)
+@pytest.mark.parametrize("kw", [{}, dict(iterations=0), dict(iterations=3, sigma_luminance=1.7, sigma_normal=0.37,
+                                                             sigma_albedo=2.0 ** -8)],
+                         ids=["defaults", "no-pass", "odd-sigmas"])
+def test_restatement_with_constant_rounds_is_the_uniform_restatement(first_half, k, kw):
+    """d_rounds == k everywhere: every plane of the uniform filter's restatement at n = first_half * 2^(k-1)."""
+    n = first_half << (k - 1)
+    A, B = uniform.sums(19, 13, n, seed=50 + k)
+    got = restate(A, B, np.full((13, 19), k, dtype=np.int32), first_half, **dict(DEFAULTS, **kw))
+    want = uniform.restate(A, B, n, **dict(DEFAULTS, **kw))
+    for plane in PLANES:
+        assert (u64(got[plane]) == u64(want[plane])).all(), plane
+    assert (got["c"].view(np.uint32) == want["c"].view(np.uint32)).all()
+
+
+def test_restatement_clamps_the_round_counts():
+    """k = min(max(rounds, 1), 32): 0 and -3 count as 1, 40 as 32; n_p is a 64-bit integer."""
+    r = np.array([[0, -3, 1, 2, 5, 32, 40]], dtype=np.int32)
+    assert counts(r, 3).tolist() == [[3, 3, 3, 6, 48, 3 << 31, 3 << 31]]
+    assert counts(r, 3).dtype == np.int64
+
+
+def test_new_kernels_use_no_scratch_and_keep_their_twins_occupancy():
+    """The resource-usage target's line for rt_vdenoise.hip (the Makefile's own
+    flags): the per-pixel prepare and finish kernels spill nothing, use no
+    scratch, and reach at least the occupancy of the uniform forms."""
+    mk = ["make", "-C", os.path.join(ROOT, "tipe-raytracer_amd")]
+    lines = subprocess.run(mk + ["-n", "-B", "resource-usage"], capture_output=True, text=True, check=True).stdout
+    cmd = [ln for ln in lines.splitlines() if "rt_vdenoise.hip" in ln and "kernel-resource-usage" in ln]
+    assert len(cmd) == 1, lines
+    out = subprocess.run(cmd[0], shell=True, cwd=os.path.join(ROOT, "tipe-raytracer_amd"), capture_output=True,
+                         text=True)
+    txt = out.stdout + out.stderr
+    assert out.returncode == 0, txt[-2000:]
+
+    def usage(name):
+        m = re.search(r"Function Name: \S*vdenoise_" + name + r"E.*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?"
+                      r"Occupancy \[waves/SIMD\]: (\d+).*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", txt, re.S)
+        assert m, (name, txt[-2000:])
+        return dict(zip(("vgprs", "scratch", "occupancy", "sgpr_spill", "spill"), map(int, m.groups())))
+
+    for new, twin in (("prepare_px_kernel", "prepare_kernel"), ("finish_px_kernel", "finish_kernel")):
+        a, b = usage(new), usage(twin)
+        print(new, a, "twin", b)
+        assert (a["scratch"], a["spill"], a["sgpr_spill"]) == (0, 0, 0), (new, a)
+        assert a["occupancy"] >= b["occupancy"], (new, a, b)
+
+
+# ---- on the GPU: seeded sums ----------------------------------------------------
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("first_half,k", UNIFORM_CASES)
+def test_uniform_rounds_equal_the_existing_filter(first_half, k):
+    """d_rounds == k: exactly rt_vdenoise_async(spp_half = first_half * 2^(k-1)) on all four planes."""
+    W, H = 64, 48
+    n = first_half << (k - 1)
+    A, B = uniform.sums(W, H, n, seed=60 + k)
+    want = uniform.device_vdenoise(A, B, n)
+    got, _ = device_filter(A, B, np.full((H, W), k, dtype=np.int32), first_half)
+    assert_planes(got, want)
+    assert set(got) == set(PLANES)
+
+
+MIXED = [(1, 1, 4), (5, 3, 4),          # only the centre tap; smaller than the footprint
+         (257, 3, 3),                   # past four 64-wide tiles, more than one block
+         (67, 35, 5),                   # the last tiled step, 16
+         (70, 40, 6),                   # step 32: the first plain-form pass
+         (67, 35, 0)]                   # no pass: the unfiltered float mean
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,H,iterations", MIXED)
+def test_mixed_rounds_equal_the_restatement(W, H, iterations):
+    """Seeded k in 1..5 per pixel, first_half 3 (n_p no power of two: rap is rounded)."""
+    A, B, rounds, want = case(W, H, 3, 700 + W + iterations, iterations)
+    assert W * H == 1 or len(np.unique(rounds)) > 1
+    got, _ = device_filter(A, B, rounds, 3, iterations=iterations)
+    assert_planes(got, want)
+
+
+@pytest.mark.gpu
+def test_mixed_rounds_canva_only():
+    A, B, rounds, want = case(67, 35, 3, 700 + 67 + 5, 5)
+    got, _ = device_filter(A, B, rounds, 3, planes=("canva",), iterations=5)
+    assert set(got) == {"canva"}
+    assert_planes(got, want)
+
+
+@pytest.mark.gpu
+def test_mixed_rounds_with_other_sigmas():
+    sigmas = (1.7, 0.37, 2.0 ** -8)
+    A, B, rounds, want = case(257, 3, 8, 710, 3, sigmas)
+    got, _ = device_filter(A, B, rounds, 8, **kwargs_of(3, sigmas))
+    assert_planes(got, want)
+
+
+@pytest.mark.gpu
+def test_round_counts_are_clamped_and_the_inputs_stay():
+    """Rounds of 0, -3 and 40 in a few pixels give the restatement's clamped
+    result; A, B and d_rounds are bit-identical after the call."""
+    W, H = 23, 9
+    rounds = mixed_rounds(W, H, 720)
+    for (y, x), v in zip(((0, 0), (3, 7), (8, 22), (4, 4), (5, 11)), (0, -3, 40, 40, 0)):
+        rounds[y, x] = v
+    A, B = sums(rounds, 3, 721)
+    want = restate(A, B, rounds, 3, **DEFAULTS)
+    got, (dA, dB, dR, _) = device_filter(A, B, rounds, 3)
+    assert_planes(got, want)
+    assert (u64(dA.cpu().numpy()) == u64(A)).all() and (u64(dB.cpu().numpy()) == u64(B)).all()
+    assert (dR.cpu().numpy() == rounds).all()
+
+
+# ---- on the GPU: the composition with rt_adaptive_async ------------------------
+
+SIZE = (64, 48)
+SEEDS = (7, 8, 9, 10)
+
+
+def bundle_of(scene):
+    return helpers.cornell() if scene == "cornell" else helpers.pyramid_scene()
+
+
+def composed(scene, ap, chunks=1):
+    """rt_adaptive_async(frame = NULL), then rt_vdenoise_adaptive_async, on a
+    side stream with no synchronisation in between and both workspaces filled
+    with 0xFF bytes: host arrays (A, B, rounds, {plane: array})."""
+    import torch
+    W, H = SIZE
+    p = helpers.params(W, H, 1, 6, seed=SEEDS[0], chunks=chunks)
+    L = tipe_rt.lib()
+    ds = tipe_rt.DeviceScene(bundle_of(scene).scene, 0)
+    try:
+        st = torch.cuda.Stream()
+        abytes, vbytes = L.rt_adaptive_workspace_bytes(W, H), L.rt_vdenoise_workspace_bytes(W, H)
+        with torch.cuda.stream(st):
+            acc = torch.full((2, H, W, 9), float("nan"), dtype=torch.float64, device="cuda:0")   # zeroed by the loop
+            rounds = torch.full((H, W), -7, dtype=torch.int32, device="cuda:0")
+            aws = torch.full((abytes,), 0xFF, dtype=torch.uint8, device="cuda:0")
+            vws = torch.full((vbytes,), 0xFF, dtype=torch.uint8, device="cuda:0")
+            out = {k: torch.full((H, W, 3), -7.0, dtype=torch.float64, device="cuda:0") for k in PLANES}
+        tipe_rt.adaptive_async(ds, p, ap, acc[0].data_ptr(), acc[1].data_ptr(), rounds.data_ptr(), aws.data_ptr(),
+                               abytes, stream=st.cuda_stream)
+        tipe_rt.vdenoise_adaptive_async(W, H, acc[0].data_ptr(), acc[1].data_ptr(), rounds.data_ptr(), ap.first_half,
+                                        params_of(), vws.data_ptr(), vbytes, *[out[k].data_ptr() for k in PLANES],
+                                        stream=st.cuda_stream)
+        torch.cuda.synchronize()
+        host = acc.cpu().numpy()
+        return host[0], host[1], rounds.cpu().numpy(), {k: t.cpu().numpy() for k, t in out.items()}
+    finally:
+        ds.close()
+
+
+def check_host_entry(scene, ap, chunks, rounds, planes):
+    p = helpers.params(*SIZE, 1, 6, seed=SEEDS[0], chunks=chunks)
+    host = tipe_rt.render_adaptive_vdenoised(bundle_of(scene).scene, p, ap)
+    for k, g in zip(("canva", "albedo", "normal"), host[:3]):
+        assert (u64(g) == u64(planes[k])).all(), k
+    assert (host[3] == rounds).all()
+    assert (tipe_rt.render_adaptive(bundle_of(scene).scene, p, ap)[3] == host[3]).all()
+    only = tipe_rt.render_adaptive_vdenoised(bundle_of(scene).scene, p, ap, albedo=False, normal=False)
+    assert only[1] is None and only[2] is None and (u64(only[0]) == u64(planes["canva"])).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene", ["cornell", "pyramid"])
+def test_composition_with_the_adaptive_loop(scene):
+    ap = tipe_rt.adaptive_params(first_half=8, max_rounds=5, tolerance=1.0 / 16.0)
+    A, B, rounds, planes = composed(scene, ap)
+    assert len(np.unique(rounds)) >= 3, np.unique(rounds)
+    assert_planes(planes, restate(A, B, rounds, ap.first_half, **DEFAULTS))
+    check_host_entry(scene, ap, 1, rounds, planes)
+
+
+@pytest.mark.gpu
+def test_host_path_with_the_default_sample_grouping():
+    """spp_chunks = RT_SPP_CHUNKS_AUTO, what rt_params_init sets: the host path against the device composition."""
+    ap = tipe_rt.adaptive_params(first_half=8, max_rounds=5, tolerance=1.0 / 16.0)
+    A, B, rounds, planes = composed("pyramid", ap, chunks=T.RT_SPP_CHUNKS_AUTO)
+    assert_planes(planes, restate(A, B, rounds, ap.first_half, **DEFAULTS))
+    check_host_entry("pyramid", ap, T.RT_SPP_CHUNKS_AUTO, rounds, planes)
+
+
+# ---- on the GPU: quality, measured in the run -----------------------------------
+
+@functools.lru_cache(maxsize=None)
+def converged(scene):
+    """The 2048-spp canva at seed 1010."""
+    return tipe_rt.render_rows(bundle_of(scene).scene, helpers.params(*SIZE, 2048, 6, seed=1010, chunks=1))[0]
+
+
+def rmse(canva, truth):
+    return float(np.sqrt(np.mean(((canva - truth) / 255.0) ** 2)))
+
+
+def measure(scene, ap):
+    """(filtered adaptive RMSE, unfiltered adaptive RMSE, mean count, uniform
+    count, RMSEs of rt_render_vdenoised at that count per seed); prints them."""
+    truth = converged(scene)
+    bundle = bundle_of(scene)
+    p = helpers.params(*SIZE, 1, 6, seed=SEEDS[0])
+    plain, _, _, rounds = tipe_rt.render_adaptive(bundle.scene, p, ap)
+    filtered, _, _, rounds_f = tipe_rt.render_adaptive_vdenoised(bundle.scene, p, ap)
+    assert (rounds == rounds_f).all()
+    mean = float((2 * ap.first_half * 2.0 ** (rounds - 1)).mean())
+    S = int(np.ceil(mean / 2.0)) * 2
+    uni = [rmse(tipe_rt.render_vdenoised(bundle.scene, helpers.params(*SIZE, S, 6, seed=s, chunks=1))[0], truth)
+           for s in SEEDS]
+    f, u0 = rmse(filtered, truth), rmse(plain, truth)
+    u = float(np.mean(uni))
+    m = (max(uni) - min(uni)) / u
+    print("%s (%d, %d, %g): adaptive RMSE unfiltered %.5f, filtered %.5f at a mean of %.2f samples per pixel; "
+          "rt_render_vdenoised at %d spp: %s, mean %.5f, spread m = %.3f, bar %.5f"
+          % (scene, ap.first_half, ap.max_rounds, ap.tolerance, u0, f, mean, S, ["%.5f" % x for x in uni], u, m,
+             u * (1.0 + m)))
+    return f, u0, u, m
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tolerance", [1.0 / 64.0, 1.0 / 16.0], ids=["tol-1/64", "tol-1/16"])
+@pytest.mark.parametrize("scene", ["cornell", "pyramid"])
+def test_filtered_adaptive_frame_matches_a_filtered_uniform_one(scene, tolerance):
+    """64x48 against 2048 spp at seed 1010, RMSE of canva / 255, adaptive at
+    (8, 5, tolerance) and seed 7.  (a) filtered < unfiltered, margin 0.
+    (b) filtered <= u (1 + m): u the mean and m = (max - min) / mean of the RMSE
+    of rt_render_vdenoised frames (the existing uniform path) at the smallest
+    even count at or above the adaptive mean, seeds 7-10."""
+    f, u0, u, m = measure(scene, tipe_rt.adaptive_params(first_half=8, max_rounds=5, tolerance=tolerance))
+    assert f < u0, (f, u0)
+    assert f <= u * (1.0 + m), (f, u, m)
+
+
+@pytest.mark.gpu
+def test_the_recorded_limit_at_a_small_first_half_is_printed():
+    """(2, 4, 1/4): pixels that stopped because their two halves happened to
+    agree carry an underestimated variance and are left alone (rt.h, "a known
+    limit").  The figures are printed, not asserted."""
+    f, u0, u, m = measure("cornell", tipe_rt.adaptive_params(first_half=2, max_rounds=4, tolerance=0.25))
+    assert all(math.isfinite(x) for x in (f, u0, u, m))

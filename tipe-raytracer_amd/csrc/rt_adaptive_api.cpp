@@ -2,8 +2,10 @@
 // "adaptive sampling"; kernels: rt_adaptive.hip): samples for a list of pixels
 // (rt_accumulate_list_async), the selection pass (rt_adaptive_select_async),
 // the loop over both (rt_adaptive_async), its resolve
-// (rt_resolve_adaptive_async) and the whole-frame render into host arrays
-// (rt_render_adaptive).
+// (rt_resolve_adaptive_async) and the whole-frame renders into host arrays
+// (rt_render_adaptive; rt_render_adaptive_vdenoised, which filters the result
+// with rt_vdenoise_adaptive_async of rt_denoise_api.cpp).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -120,6 +122,68 @@ int launch_list_on_stream(KParams& kp, const double* uni, const unsigned* d_list
     if (d_part) (void)hipFreeAsync(d_part, st);
     (void)hipFreeAsync(d_uni, st);
     if (e != hipSuccess) return fail(RT_EDEVICE, "list render launch: %s", hipGetErrorString(e));
+    return RT_OK;
+}
+
+// rt_render_adaptive (filter false: the planes are rt_resolve_adaptive_async's, vparams is not read) and
+// rt_render_adaptive_vdenoised (the planes are rt_vdenoise_adaptive_async's): the loop on rt_init's first
+// device with the cached scene, a pooled stream and pinned staging; copies out only on success.  `what`
+// names the entry point in messages.
+int render_adaptive_host(const char* what, const rt_scene* scene, const rt_params* params,
+                         const rt_adaptive_params* aparams, const rt_vdenoise_params* vparams, bool filter,
+                         rt_color* canva, rt_color* albedo, rt_color* normal, int* rounds)
+{
+    int rc, dev;
+    if ((rc = validate_scene(scene))) return rc;
+    if (!params) return fail(RT_EINVAL, "params is NULL");
+    if ((rc = validate_adaptive(aparams))) return rc;
+    rt_params batch = *params;
+    batch.nbRayonParPixel = aparams->first_half;
+    if ((rc = validate_params(&batch))) return rc;
+    if (batch.semantics == RT_SEM_CUDA) return fail(RT_EUNSUPPORTED, "%s renders RT_SEM_MAIN_C only", what);
+    const int W = batch.largeur_image, H = batch.hauteur_image;
+    if ((rc = validate_frame(W, H))) return rc;
+    if (filter && (rc = validate_vdenoise(W, H, vparams))) return rc;
+    if (!canva) return fail(RT_EINVAL, "adaptive: canva is NULL");
+    if ((rc = first_device(dev))) return rc;
+    std::shared_ptr<rt_device_scene> sc;
+    if ((rc = scene_cache_get(dev, scene, sc))) return rc;
+    StreamLease ps;                  // drained on every return: the caller reads canva next
+    if ((rc = ps.acquire(dev, true))) return rc;
+    DeviceGuard g(dev);
+    const size_t npx = (size_t)W * H, plane = npx * sizeof(rt_color), sums = npx * 9 * sizeof(double);
+    const size_t rbytes = (npx * sizeof(int) + 15) / 16 * 16, aws_bytes = rt_adaptive_workspace_bytes(W, H);
+    // the filter runs behind the loop on the same stream: one workspace serves both, the larger one's size
+    const size_t vws_bytes = filter ? rt_vdenoise_workspace_bytes(W, H) : 0;
+    const size_t ws_bytes = (std::max(aws_bytes, vws_bytes) + 15) / 16 * 16;
+    rt_color* const dst[3] = {canva, albedo, normal};
+    StreamBuffer dbuf;               // device: the two accumulators, the workspace, the round counts, the planes
+    hipError_t e = ps->reserve_host(3 * plane + rbytes);
+    if (e == hipSuccess) e = dbuf.alloc(2 * sums + ws_bytes + rbytes + 3 * plane, ps->st, dev);
+    if (e != hipSuccess) return fail(RT_ENOMEM, "adaptive buffers: %s", hipGetErrorString(e));
+    char* buf = (char*)dbuf.p;
+    double* acc[2] = {(double*)buf, (double*)(buf + sums)};
+    char* ws = buf + 2 * sums;
+    int* d_rounds = (int*)(ws + ws_bytes);
+    char* planes = ws + ws_bytes + rbytes;
+    const rt_frame fr = {(rt_color*)planes, albedo ? (rt_color*)(planes + plane) : nullptr,
+                         normal ? (rt_color*)(planes + 2 * plane) : nullptr, nullptr};
+    if ((rc = rt_adaptive_async(sc.get(), params, aparams, acc[0], acc[1], d_rounds, ws, aws_bytes,
+                                filter ? nullptr : &fr, ps->st)))
+        return rc;
+    if (filter && (rc = rt_vdenoise_adaptive_async(W, H, acc[0], acc[1], d_rounds, aparams->first_half, vparams, ws,
+                                                   vws_bytes, &fr, ps->st)))
+        return rc;
+    char* host = (char*)ps->host;
+    for (int pl = 0; pl < 3 && e == hipSuccess; ++pl)
+        if (dst[pl]) e = hipMemcpyAsync(host + pl * plane, planes + pl * plane, plane, hipMemcpyDeviceToHost, ps->st);
+    if (rounds && e == hipSuccess)
+        e = hipMemcpyAsync(host + 3 * plane, d_rounds, npx * sizeof(int), hipMemcpyDeviceToHost, ps->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(ps->st);
+    if (e != hipSuccess) return fail(RT_EDEVICE, "adaptive: %s", hipGetErrorString(e));
+    for (int pl = 0; pl < 3; ++pl)
+        if (dst[pl]) std::memcpy(dst[pl], host + pl * plane, plane);
+    if (rounds) std::memcpy(rounds, host + 3 * plane, npx * sizeof(int));
     return RT_OK;
 }
 
@@ -266,50 +330,16 @@ int rt_adaptive_async(const rt_device_scene* scene, const rt_params* params, con
 int rt_render_adaptive(const rt_scene* scene, const rt_params* params, const rt_adaptive_params* aparams,
                        rt_color* canva, rt_color* albedo, rt_color* normal, int* rounds)
 {
-    int rc, dev;
-    if ((rc = validate_scene(scene))) return rc;
-    if (!params) return fail(RT_EINVAL, "params is NULL");
-    if ((rc = validate_adaptive(aparams))) return rc;
-    rt_params batch = *params;
-    batch.nbRayonParPixel = aparams->first_half;
-    if ((rc = validate_params(&batch))) return rc;
-    if (batch.semantics == RT_SEM_CUDA) return fail(RT_EUNSUPPORTED, "rt_render_adaptive renders RT_SEM_MAIN_C only");
-    const int W = batch.largeur_image, H = batch.hauteur_image;
-    if ((rc = validate_frame(W, H))) return rc;
-    if (!canva) return fail(RT_EINVAL, "adaptive: canva is NULL");
-    if ((rc = first_device(dev))) return rc;
-    std::shared_ptr<rt_device_scene> sc;
-    if ((rc = scene_cache_get(dev, scene, sc))) return rc;
-    StreamLease ps;                  // drained on every return: the caller reads canva next
-    if ((rc = ps.acquire(dev, true))) return rc;
-    DeviceGuard g(dev);
-    const size_t npx = (size_t)W * H, plane = npx * sizeof(rt_color), sums = npx * 9 * sizeof(double);
-    const size_t rbytes = (npx * sizeof(int) + 15) / 16 * 16, ws_bytes = rt_adaptive_workspace_bytes(W, H);
-    rt_color* const dst[3] = {canva, albedo, normal};
-    StreamBuffer dbuf;               // device: the two accumulators, the workspace, the round counts, the planes
-    hipError_t e = ps->reserve_host(3 * plane + rbytes);
-    if (e == hipSuccess) e = dbuf.alloc(2 * sums + ws_bytes + rbytes + 3 * plane, ps->st, dev);
-    if (e != hipSuccess) return fail(RT_ENOMEM, "adaptive buffers: %s", hipGetErrorString(e));
-    char* buf = (char*)dbuf.p;
-    char* ws = buf + 2 * sums;
-    int* d_rounds = (int*)(ws + ws_bytes);
-    char* planes = ws + ws_bytes + rbytes;
-    const rt_frame fr = {(rt_color*)planes, albedo ? (rt_color*)(planes + plane) : nullptr,
-                         normal ? (rt_color*)(planes + 2 * plane) : nullptr, nullptr};
-    if ((rc = rt_adaptive_async(sc.get(), params, aparams, (double*)buf, (double*)(buf + sums), d_rounds, ws, ws_bytes,
-                                &fr, ps->st)))
-        return rc;
-    char* host = (char*)ps->host;
-    for (int pl = 0; pl < 3 && e == hipSuccess; ++pl)
-        if (dst[pl]) e = hipMemcpyAsync(host + pl * plane, planes + pl * plane, plane, hipMemcpyDeviceToHost, ps->st);
-    if (rounds && e == hipSuccess)
-        e = hipMemcpyAsync(host + 3 * plane, d_rounds, npx * sizeof(int), hipMemcpyDeviceToHost, ps->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(ps->st);
-    if (e != hipSuccess) return fail(RT_EDEVICE, "adaptive: %s", hipGetErrorString(e));
-    for (int pl = 0; pl < 3; ++pl)
-        if (dst[pl]) std::memcpy(dst[pl], host + pl * plane, plane);
-    if (rounds) std::memcpy(rounds, host + 3 * plane, npx * sizeof(int));
-    return RT_OK;
+    return render_adaptive_host("rt_render_adaptive", scene, params, aparams, nullptr, false, canva, albedo, normal,
+                                rounds);
+}
+
+int rt_render_adaptive_vdenoised(const rt_scene* scene, const rt_params* params, const rt_adaptive_params* aparams,
+                                 const rt_vdenoise_params* vparams, rt_color* canva, rt_color* albedo,
+                                 rt_color* normal, int* rounds)
+{
+    return render_adaptive_host("rt_render_adaptive_vdenoised", scene, params, aparams, vparams, true, canva, albedo,
+                                normal, rounds);
 }
 
 }  // extern "C"

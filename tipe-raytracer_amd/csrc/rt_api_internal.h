@@ -66,6 +66,7 @@ int first_device(int& dev);
 
 int validate_scene(const rt_scene* sc);
 int validate_params(const rt_params* p);
+int validate_vdenoise(int W, int H, const rt_vdenoise_params* p);    // rt_denoise_api.cpp: the frame size too
 
 // rt_launch_plan.h's fill_kparams on an uploaded scene, with rt_set_zero_throughput_exit's switch;
 // launch_on_stream plans the launch (plan_render) and runs its bands.

@@ -3,8 +3,9 @@
 // the built-in edge-avoiding a-trous filter (rt_denoise.hip) on a device
 // frame (rt_denoise_async), on host arrays (rt_denoise_host) and as a hook
 // (rt_denoise_atrous); and the variance-guided denoiser (rt_vdenoise.hip) on
-// two device accumulators (rt_vdenoise_async) and as a whole-frame render
-// into host arrays (rt_render_vdenoised).
+// two device accumulators (rt_vdenoise_async; rt_vdenoise_adaptive_async with
+// each pixel's own sample count) and as a whole-frame render into host arrays
+// (rt_render_vdenoised).
 #include <atomic>
 #include <cmath>
 #include <cstring>
@@ -53,10 +54,12 @@ int validate_denoise(int W, int H, const rt_denoise_params* p)
     return validate_passes(p->iterations, 1, sig, name);
 }
 
-// ... and of the variance-guided one
 constexpr rt_vdenoise_params kVDefaults = {4, 4.0f, 0.5f, 0.25f};
 
-int validate_vdenoise(int W, int H, const rt_vdenoise_params* p)
+}  // namespace
+
+// ... and of the variance-guided one (rt_adaptive_api.cpp validates with it too)
+int rt::validate_vdenoise(int W, int H, const rt_vdenoise_params* p)
 {
     const int rc = validate_frame_size(W, H);
     if (rc) return rc;
@@ -64,6 +67,31 @@ int validate_vdenoise(int W, int H, const rt_vdenoise_params* p)
     const float sig[3] = {p->sigma_luminance, p->sigma_normal, p->sigma_albedo};
     const char* const name[3] = {"sigma_luminance", "sigma_normal", "sigma_albedo"};
     return validate_passes(p->iterations, 0, sig, name);
+}
+
+namespace {
+
+// rt_vdenoise_async (rounds null, n = spp_half) and rt_vdenoise_adaptive_async (n = first_half): what both
+// refuse, then the launches
+int vdenoise_on_stream(int W, int H, const double* d_sums_a, const double* d_sums_b, const int* d_rounds, int n,
+                       const char* n_name, const rt_vdenoise_params* params, void* workspace, size_t workspace_bytes,
+                       const rt_frame* out, void* hip_stream)
+{
+    const int rc = validate_vdenoise(W, H, params);
+    if (rc) return rc;
+    if (!d_sums_a || !d_sums_b) return fail(RT_EINVAL, "vdenoise: an accumulator is NULL");
+    if (n < 1) return fail(RT_EINVAL, "vdenoise: %s %d < 1", n_name, n);
+    if (!out || !out->canva) return fail(RT_EINVAL, "vdenoise: out.canva is NULL");
+    if (!workspace) return fail(RT_EINVAL, "vdenoise: workspace is NULL");
+    if ((uintptr_t)workspace % 16) return fail(RT_EINVAL, "vdenoise: workspace is not 16-byte aligned");
+    if (workspace_bytes < rt_vdenoise_workspace_bytes(W, H))
+        return fail(RT_EINVAL, "vdenoise: workspace of %zu bytes, %dx%d needs %zu", workspace_bytes, W, H,
+                    rt_vdenoise_workspace_bytes(W, H));
+    const int e = launch_vdenoise(W, H, d_sums_a, d_sums_b, d_rounds, n, params->iterations, params->sigma_luminance,
+                                  params->sigma_normal, params->sigma_albedo, (float*)workspace, (double*)out->canva,
+                                  (double*)out->albedo, (double*)out->normal, (double*)out->radiance, hip_stream);
+    if (e) return fail(RT_EDEVICE, "vdenoise launch: %s", hipGetErrorString((hipError_t)e));
+    return RT_OK;
 }
 
 }  // namespace
@@ -210,21 +238,17 @@ int rt_vdenoise_async(int W, int H, const double* d_sums_a, const double* d_sums
                       const rt_vdenoise_params* params, void* workspace, size_t workspace_bytes, const rt_frame* out,
                       void* hip_stream)
 {
-    const int rc = validate_vdenoise(W, H, params);
-    if (rc) return rc;
-    if (!d_sums_a || !d_sums_b) return fail(RT_EINVAL, "vdenoise: an accumulator is NULL");
-    if (spp_half < 1) return fail(RT_EINVAL, "vdenoise: spp_half %d < 1", spp_half);
-    if (!out || !out->canva) return fail(RT_EINVAL, "vdenoise: out.canva is NULL");
-    if (!workspace) return fail(RT_EINVAL, "vdenoise: workspace is NULL");
-    if ((uintptr_t)workspace % 16) return fail(RT_EINVAL, "vdenoise: workspace is not 16-byte aligned");
-    if (workspace_bytes < rt_vdenoise_workspace_bytes(W, H))
-        return fail(RT_EINVAL, "vdenoise: workspace of %zu bytes, %dx%d needs %zu", workspace_bytes, W, H,
-                    rt_vdenoise_workspace_bytes(W, H));
-    const int e = launch_vdenoise(W, H, d_sums_a, d_sums_b, spp_half, params->iterations, params->sigma_luminance,
-                                  params->sigma_normal, params->sigma_albedo, (float*)workspace, (double*)out->canva,
-                                  (double*)out->albedo, (double*)out->normal, (double*)out->radiance, hip_stream);
-    if (e) return fail(RT_EDEVICE, "vdenoise launch: %s", hipGetErrorString((hipError_t)e));
-    return RT_OK;
+    return vdenoise_on_stream(W, H, d_sums_a, d_sums_b, nullptr, spp_half, "spp_half", params, workspace,
+                              workspace_bytes, out, hip_stream);
+}
+
+int rt_vdenoise_adaptive_async(int W, int H, const double* d_sums_a, const double* d_sums_b, const int* d_rounds,
+                               int first_half, const rt_vdenoise_params* params, void* workspace,
+                               size_t workspace_bytes, const rt_frame* out, void* hip_stream)
+{
+    if (!d_rounds) return fail(RT_EINVAL, "vdenoise: d_rounds is NULL");
+    return vdenoise_on_stream(W, H, d_sums_a, d_sums_b, d_rounds, first_half, "first_half", params, workspace,
+                              workspace_bytes, out, hip_stream);
 }
 
 int rt_render_vdenoised(const rt_scene* scene, const rt_params* params, const rt_vdenoise_params* vparams,

@@ -205,11 +205,13 @@ int launch_denoise(int W, int H, double* canva, const double* albedo, const doub
                    void* stream);
 // launchers (rt_vdenoise.hip): the variance-guided denoiser (rt.h "variance-guided denoiser") on two device
 // accumulators.  The workspace holds four planes of denoise_plane_floats(W*H) floats, then three of
-// vdenoise_scalar_floats(W*H); albedo / normal / radiance may be null.
+// vdenoise_scalar_floats(W*H); albedo / normal / radiance may be null.  rounds null: every pixel holds spp_half
+// samples per accumulator; else pixel p holds spp_half * 2^(k-1), k = rounds[p] clamped to 1..32 (rt.h
+// "per-pixel sample counts"), and spp_half is the adaptive schedule's first_half.
 size_t vdenoise_scalar_floats(long long npx);
-int launch_vdenoise(int W, int H, const double* sums_a, const double* sums_b, int spp_half, int iterations,
-                    float sigma_luminance, float sigma_normal, float sigma_albedo, float* workspace, double* canva,
-                    double* albedo, double* normal, double* radiance, void* stream);
+int launch_vdenoise(int W, int H, const double* sums_a, const double* sums_b, const int* rounds, int spp_half,
+                    int iterations, float sigma_luminance, float sigma_normal, float sigma_albedo, float* workspace,
+                    double* canva, double* albedo, double* normal, double* radiance, void* stream);
 
 // launchers (rt_adaptive.hip): adaptive sampling (rt.h "adaptive sampling").
 // What a list launch needs besides KParams, as the render kernel's second

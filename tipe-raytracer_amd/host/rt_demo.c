@@ -16,6 +16,8 @@
  * -adaptive renders through rt_render_adaptive with tolerance TOL (the other
  * parameters at their defaults; -s is ignored; one device) and also prints the
  * mean samples per pixel and the share of pixels per round count.
+ * -adaptive with -vdenoise renders through rt_render_adaptive_vdenoised: the
+ * adaptive frame filtered with each pixel's own sample count.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -66,7 +68,8 @@ int main(int argc, char** argv)
         } else {
             fprintf(stderr, "usage: %s [-w W] [-s spp] [-b bounces] [-ao I] [-o out.ppm] "
                             "[-obj f.obj -mtl f.mtl [-move x y z]] [-devices N] [-denoise [iterations]] "
-                            "[-vdenoise [iterations]] [-adaptive TOL]\n",
+                            "[-vdenoise [iterations]] [-adaptive TOL]\n"
+                            "  -adaptive with -vdenoise: the adaptive frame, filtered with each pixel's own sample count\n",
                     argv[0]);
             return 2;
         }
@@ -138,13 +141,17 @@ int main(int argc, char** argv)
     int* rounds = adaptive ? (int*)calloc(n, sizeof(int)) : NULL;
     struct timeval t0, t1;
     gettimeofday(&t0, NULL);
-    int rc = adaptive   ? rt_render_adaptive(&scene, &p, &adp, canva, albedo, normal, rounds)
-             : vdenoise ? rt_render_vdenoised(&scene, &p, &vdn, canva, albedo, normal)
-                        : rt_render_rows(&scene, &p, H - 1, 0, canva, albedo, normal);
+    const char* entry = adaptive && vdenoise ? "rt_render_adaptive_vdenoised"
+                        : adaptive           ? "rt_render_adaptive"
+                        : vdenoise           ? "rt_render_vdenoised"
+                                             : "rt_render_rows";
+    int rc = adaptive && vdenoise ? rt_render_adaptive_vdenoised(&scene, &p, &adp, &vdn, canva, albedo, normal, rounds)
+             : adaptive           ? rt_render_adaptive(&scene, &p, &adp, canva, albedo, normal, rounds)
+             : vdenoise           ? rt_render_vdenoised(&scene, &p, &vdn, canva, albedo, normal)
+                                  : rt_render_rows(&scene, &p, H - 1, 0, canva, albedo, normal);
     gettimeofday(&t1, NULL);
     if (rc) {
-        fprintf(stderr, "%s: %s\n", adaptive ? "rt_render_adaptive" : vdenoise ? "rt_render_vdenoised" : "rt_render_rows",
-                rt_last_error());
+        fprintf(stderr, "%s: %s\n", entry, rt_last_error());
         return 1;
     }
     double dt = (t1.tv_sec - t0.tv_sec) + 1e-6 * (t1.tv_usec - t0.tv_usec);
@@ -155,8 +162,8 @@ int main(int argc, char** argv)
             total += (double)adp.first_half * (double)(1 << k);
             share[k] += 1.0 / (double)n;
         }
-        fprintf(stderr, "adaptive, tolerance %g: %.2f samples per pixel on average; pixels per round count:", adp.tolerance,
-                total / (double)n);
+        fprintf(stderr, "adaptive%s, tolerance %g: %.2f samples per pixel on average; pixels per round count:",
+                vdenoise ? " + variance-guided filter" : "", adp.tolerance, total / (double)n);
         for (int k = 1; k <= adp.max_rounds; k++) fprintf(stderr, " %d: %.1f %%", k, 100.0 * share[k]);
         fprintf(stderr, "\n%dx%d, %d bounces: %.3f s, %.1f Msamples/s (end-to-end)\n", W, H, bounces, dt, total / dt / 1e6);
         free(rounds);

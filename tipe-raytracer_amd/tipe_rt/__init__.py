@@ -121,6 +121,11 @@ def lib():
                                                     P(Frame), C.c_void_p]
             L.rt_render_adaptive.argtypes = [P(Scene), P(Params), P(AdaptiveParams), C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_vdenoise_adaptive_async"):     # (added to ABI 5 as well)
+            L.rt_vdenoise_adaptive_async.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                     P(VDenoiseParams), C.c_void_p, C.c_size_t, P(Frame), C.c_void_p]
+            L.rt_render_adaptive_vdenoised.argtypes = [P(Scene), P(Params), P(AdaptiveParams), P(VDenoiseParams),
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -137,7 +142,8 @@ EXPORTED_SYMBOLS = ["rt_params_init", "rt_init", "rt_shutdown", "rt_last_error",
                     "rt_vdenoise_params_init", "rt_vdenoise_workspace_bytes", "rt_vdenoise_async",
                     "rt_render_vdenoised", "rt_accumulate_list_async", "rt_adaptive_select_async",
                     "rt_adaptive_workspace_bytes", "rt_adaptive_params_init", "rt_adaptive_async",
-                    "rt_resolve_adaptive_async", "rt_render_adaptive"]
+                    "rt_resolve_adaptive_async", "rt_render_adaptive", "rt_vdenoise_adaptive_async",
+                    "rt_render_adaptive_vdenoised"]
 
 # rt_denoise_fn (rt.h): denoiser()'s signature, denoiser.h:31
 DENOISE_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p, Camera, C.c_void_p, C.c_void_p)
@@ -317,6 +323,32 @@ def render_adaptive(scene, params, aparams=None, albedo=True, normal=True):
     check(lib().rt_render_adaptive(C.byref(scene), C.byref(params), C.byref(ap), canva.ctypes.data,
                                    alb.ctypes.data if alb is not None else None,
                                    nrm.ctypes.data if nrm is not None else None, rounds.ctypes.data))
+    return canva, alb, nrm, rounds
+
+
+def vdenoise_adaptive_async(W, H, sums_a_ptr, sums_b_ptr, rounds_ptr, first_half, params, workspace_ptr,
+                            workspace_bytes, canva_ptr, albedo_ptr=None, normal_ptr=None, radiance_ptr=None,
+                            stream=None):
+    """rt_vdenoise_adaptive_async: the variance-guided denoiser on an adaptive
+    result, pixel p holding first_half * 2^(rounds[p] - 1) samples per accumulator."""
+    fr = Frame(canva_ptr, albedo_ptr, normal_ptr, radiance_ptr)
+    check(lib().rt_vdenoise_adaptive_async(W, H, sums_a_ptr, sums_b_ptr, rounds_ptr, first_half, C.byref(params),
+                                           workspace_ptr, workspace_bytes, C.byref(fr), stream))
+
+
+def render_adaptive_vdenoised(scene, params, aparams=None, vparams=None, albedo=True, normal=True):
+    """rt_render_adaptive_vdenoised into fresh arrays: (canva, albedo, normal,
+    rounds) as render_adaptive's, the planes filtered by the variance-guided denoiser."""
+    W, H = params.largeur_image, params.hauteur_image
+    canva = np.zeros((H, W, 3))
+    alb = np.zeros((H, W, 3)) if albedo else None
+    nrm = np.zeros((H, W, 3)) if normal else None
+    rounds = np.zeros((H, W), dtype=np.int32)
+    ap = aparams if aparams is not None else adaptive_params()
+    vp = vparams if vparams is not None else vdenoise_params()
+    check(lib().rt_render_adaptive_vdenoised(C.byref(scene), C.byref(params), C.byref(ap), C.byref(vp),
+                                             canva.ctypes.data, alb.ctypes.data if alb is not None else None,
+                                             nrm.ctypes.data if nrm is not None else None, rounds.ctypes.data))
     return canva, alb, nrm, rounds
 
 

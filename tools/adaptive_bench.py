@@ -2,11 +2,15 @@
 """Time adaptive sampling (rt_adaptive_async) against uniform renders of the same scene.
 
     tools/adaptive_bench.py [--scenes box,nature] [--size 1200x900] [--reps 5] [--warmup 1] [--label TAG]
-                            [--first-half 8] [--max-rounds 5] [--tolerance 0.015625]
+                            [--first-half 8] [--max-rounds 5] [--tolerance 0.015625] [--no-rounds]
 
 Per scene, JSON lines (device-event times, every repetition listed so the spread shows):
   adaptive        rt_adaptive_async at the given parameters (A, B, d_rounds and the frame planes), its total
                   samples, the mean per pixel and the share of pixels per round count;
+  adaptive_vdenoised   rt_adaptive_async with frame = NULL followed by rt_vdenoise_adaptive_async at its defaults
+                  on the same stream (rt_render_adaptive_vdenoised's device work);
+  uniform_vdenoised    rt_render_vdenoised's device composition (two rt_accumulate_async calls +
+                  rt_vdenoise_async) at the even count nearest the adaptive frame's mean;
   uniform_max     two rt_accumulate_async calls + rt_resolve_async at the adaptive schedule's maximum count;
   uniform_mean    the same at the even count nearest the adaptive frame's mean;
   round           for each round, host-driven through the public calls (accumulate, select, one read of the
@@ -36,6 +40,7 @@ def main():
     ap.add_argument("--first-half", type=int, default=None)
     ap.add_argument("--max-rounds", type=int, default=None)
     ap.add_argument("--tolerance", type=float, default=None)
+    ap.add_argument("--no-rounds", action="store_true", help="skip the round-by-round lines")
     args = ap.parse_args()
     import torch
     import tipe_rt
@@ -114,11 +119,37 @@ def main():
 
         half_max = fh << (R - 1)
         half_mean = max(1, int(round(mean / 2.0)))
+
+        vdp = tipe_rt.vdenoise_params()
+        vbytes = tipe_rt.lib().rt_vdenoise_workspace_bytes(W, H)
+        vws = torch.empty(vbytes, dtype=torch.uint8, device=dev)
+
+        def adaptive_vdenoised():
+            tipe_rt.adaptive_async(ds, p, adp, acc[0].data_ptr(), acc[1].data_ptr(), rounds.data_ptr(), ws.data_ptr(),
+                                   nbytes, stream=st)
+            tipe_rt.vdenoise_adaptive_async(W, H, acc[0].data_ptr(), acc[1].data_ptr(), rounds.data_ptr(), fh, vdp,
+                                            vws.data_ptr(), vbytes, planes[0].data_ptr(), planes[1].data_ptr(),
+                                            planes[2].data_ptr(), stream=st)
+
+        def uniform_vdenoised():
+            acc.zero_()
+            for j in range(2):
+                tipe_rt.accumulate_async(ds, with_spp(half_mean), j * half_mean, band, acc[j].data_ptr(), st)
+            tipe_rt.vdenoise_async(W, H, acc[0].data_ptr(), acc[1].data_ptr(), half_mean, vdp, vws.data_ptr(), vbytes,
+                                   planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(), stream=st)
+
+        emit(scene=name, what="adaptive_vdenoised", ms=timed(adaptive_vdenoised), mean_spp=round(mean, 3),
+             iterations=vdp.iterations)
+        emit(scene=name, what="uniform_vdenoised", spp=2 * half_mean, ms=timed(uniform_vdenoised),
+             iterations=vdp.iterations)
         emit(scene=name, what="uniform_max", spp=2 * half_max, ms=timed(uniform(half_max)),
              total_samples=2.0 * half_max * npx)
         emit(scene=name, what="uniform_mean", spp=2 * half_mean, ms=timed(uniform(half_mean)),
              total_samples=2.0 * half_mean * npx)
 
+        if args.no_rounds:
+            ds.close()
+            continue
         # round by round through the public calls
         lst = torch.zeros(npx, dtype=torch.int32, device=dev)
         cnt = torch.zeros(4, dtype=torch.int32, device=dev)

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Per-pass kernel times of the built-in denoisers from a rocprofv3 kernel trace.
 
-    tools/denoise_trace_summary.py KERNEL_TRACE.csv [--sizes 1200x900,3840x2880] [--skip 3] [--filter atrous|vdenoise]
+    tools/denoise_trace_summary.py KERNEL_TRACE.csv [--sizes 1200x900,3840x2880] [--skip 3] [--filter atrous|vdenoise|vdenoise_px]
 
 Reads the dispatches of a `rocprofv3 --kernel-trace` run of
 tools/denoise_bench.py.  A denoise call is prepare, one pass kernel per
 iteration, finish; the frame of a call is recognised by the grid of its first
 pass (ceil(W/64) * ceil(H/4) blocks).  A call of the variance-guided filter
 (--filter vdenoise: the vdenoise_* kernels) has the variance blur (lum) in
-front of each pass kernel; it is reported next to its pass.  The first --skip
+front of each pass kernel; it is reported next to its pass.  --filter
+vdenoise_px takes the calls of rt_vdenoise_adaptive_async instead (prepare and
+finish are the _px kernels), --filter vdenoise those of rt_vdenoise_async.  The first --skip
 calls of each size are warm-up.  Prints, per size and pass, the median and
 minimum kernel time and the compulsory-traffic rate (48 B/pixel for the
 a-trous pass, 68 B/pixel for the variance-guided pass with its blur) / median
@@ -26,9 +28,9 @@ def main():
     ap.add_argument("trace")
     ap.add_argument("--sizes", default="1200x900,3840x2880")
     ap.add_argument("--skip", type=int, default=3)
-    ap.add_argument("--filter", choices=("atrous", "vdenoise"), default="atrous")
+    ap.add_argument("--filter", choices=("atrous", "vdenoise", "vdenoise_px"), default="atrous")
     args = ap.parse_args()
-    vd = args.filter == "vdenoise"
+    vd, px = args.filter != "atrous", args.filter == "vdenoise_px"
     pass_bytes = 68.0 if vd else 48.0
     sizes = {}
     for s in args.sizes.split(","):
@@ -43,7 +45,9 @@ def main():
         us = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
         short = ("prepare" if "prepare" in name else "finish" if "finish" in name else
                  "lum" if "_lum_" in name else "tiled" if "tiled" in name else "plain")
-        if short == "prepare":
+        if short == "prepare" and ("prepare_px" in name) != px:
+            cur = None                           # the other form's call
+        elif short == "prepare":
             cur = {"prepare": us, "passes": [], "lum": [], "grid0": None, "t0": int(r["Start_Timestamp"])}
         elif cur is not None and short == "finish":
             cur["finish"] = us
