@@ -412,7 +412,11 @@ int rt_count_async(const rt_device_scene* scene, const rt_params* params,
  * keyed by the global sample index, so with spp_chunks = 1 the sums after any
  * sequence of batches covering samples 0..S-1 in order are bit-identical to
  * one launch of S samples (fill_canva's fold continues across batches).  With
- * spp_chunks = P > 1 a batch adds its P slice sums in slice order.  The sums
+ * spp_chunks = P > 1 a batch adds its P slice sums in slice order: the slices
+ * are rt_chunk_bound's of the batch's own nbRayonParPixel (P resolved from it
+ * by rt_resolve_spp_chunks), each slice sum starts from +0.0 and takes its
+ * samples in order, then sums = sums + slice_c for c = 0 .. P-1 (so a slice sum
+ * is never -0.0, and a sum that starts as -0.0 ends as +0.0).  The sums
  * are plain memory: copy them out to checkpoint, back in to resume.
  * sample_offset + nbRayonParPixel must not exceed 2^32. */
 int rt_accumulate_async(const rt_device_scene* scene, const rt_params* params, long long sample_offset,

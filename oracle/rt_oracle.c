@@ -793,11 +793,36 @@ static void init_ctx(ctx* c, const band* b)
     }
 }
 
+/* One sample of pixel (i, j): the stream (seed, pixel, sample), the camera
+ * draws, the tracer.  The one per-sample step of every entry point. */
+static void trace_pixel_sample(ctx* c, const band* b, int i, int j, uint32_t pixel, uint32_t sample, rt_color smp[3])
+{
+    const rt_params* p = b->p;
+    const int W = p->largeur_image, H = p->hauteur_image;
+    c->pixel = pixel;
+    c->sample = sample;
+    c->n = 0;
+    c->cnt[RT_CNT_SAMPLES]++;
+    double u, v;
+    if (c->cuda) {                      /* main_cuda.cu:152-153 */
+        u = ((double)i + 0.5 + random_double(c, -0.5, 0.5)) / (W - 1);
+        v = ((double)j + 0.5 + random_double(c, -0.5, 0.5)) / (H - 1);
+    } else {                           /* main.c:265-266 */
+        u = ((double)i + random_double(c, -0.5, 0.5)) / (W - 1);
+        v = ((double)j + random_double(c, -0.5, 0.5)) / (H - 1);
+    }
+    double dx = random_double(c, -0.5, 0.5) * b->ox;
+    double dy = random_double(c, -0.5, 0.5) * b->oy;
+    rt_ray r = get_ray(u, v, &p->cam, b->focus, dx, dy);
+    if (c->cuda) tracer_cuda(c, r, smp);
+    else tracer(c, r, smp);
+}
+
 static void* band_worker(void* arg)
 {
     band* b = (band*)arg;
     const rt_params* p = b->p;
-    const int W = p->largeur_image, H = p->hauteur_image, S = p->nbRayonParPixel;
+    const int W = p->largeur_image, S = p->nbRayonParPixel;
     ctx c;
     init_ctx(&c, b);
     /* rt.h spp_chunks: P > 1 sums samples in P fixed slices, then the slice
@@ -811,24 +836,8 @@ static void* band_worker(void* arg)
                 const int s0 = (int)rt_chunk_bound(ch, S, P), s1 = (int)rt_chunk_bound(ch + 1, S, P);
                 rt_color part[3] = {v3(0, 0, 0), v3(0, 0, 0), v3(0, 0, 0)};
                 for (int x = s0; x < s1; ++x) {
-                    c.pixel = (uint32_t)pixel_index;
-                    c.sample = (uint32_t)x;
-                    c.n = 0;
-                    c.cnt[RT_CNT_SAMPLES]++;
-                    double u, v;
-                    if (c.cuda) {                      /* main_cuda.cu:152-153 */
-                        u = ((double)i + 0.5 + random_double(&c, -0.5, 0.5)) / (W - 1);
-                        v = ((double)j + 0.5 + random_double(&c, -0.5, 0.5)) / (H - 1);
-                    } else {                           /* main.c:265-266 */
-                        u = ((double)i + random_double(&c, -0.5, 0.5)) / (W - 1);
-                        v = ((double)j + random_double(&c, -0.5, 0.5)) / (H - 1);
-                    }
-                    double dx = random_double(&c, -0.5, 0.5) * b->ox;
-                    double dy = random_double(&c, -0.5, 0.5) * b->oy;
-                    rt_ray r = get_ray(u, v, &p->cam, b->focus, dx, dy);
                     rt_color smp[3];
-                    if (c.cuda) tracer_cuda(&c, r, smp);
-                    else tracer(&c, r, smp);
+                    trace_pixel_sample(&c, b, i, j, (uint32_t)pixel_index, (uint32_t)x, smp);
                     part[0] = add(part[0], smp[0]);
                     part[1] = add(part[1], smp[1]);
                     part[2] = add(part[2], smp[2]);
@@ -873,6 +882,26 @@ static int validate(const rt_scene* sc, const rt_params* p)
     return RT_OK;
 }
 
+/* The launch constants of a band: the scene, the parameters and ThreadData's
+ * int fields (main.c:42-43). */
+static void band_init(band* b, const rt_scene* scene, const rt_params* params)
+{
+    memset(b, 0, sizeof *b);
+    b->sc = scene;
+    b->p = params;
+    b->focus = params->focus_distance;
+    b->ox = params->ouverture_x;
+    b->oy = params->ouverture_y;
+    b->AO = params->AO_intensity;
+    if (params->compat_int_truncation && params->semantics != RT_SEM_CUDA) {   /* ThreadData int fields, main.c:42-43 */
+        b->focus = (double)(int)b->focus;
+        b->ox = (double)(int)b->ox;
+        b->oy = (double)(int)b->oy;
+        b->AO = (double)(int)b->AO;
+    }
+    b->portable = g_math_mode >= 0 ? g_math_mode : (params->rng == RT_RNG_PHILOX);
+}
+
 int oracle_render_rows(const rt_scene* scene, const rt_params* params, int row_hi, int row_lo, int nthreads,
                        int reseed, rt_color* canva, rt_color* albedo, rt_color* normal, rt_color* radiance,
                        unsigned long long* counters)
@@ -884,15 +913,8 @@ int oracle_render_rows(const rt_scene* scene, const rt_params* params, int row_h
     if (nthreads < 1) nthreads = 1;
     if (nthreads > nrows) nthreads = nrows;
 
-    double focus = params->focus_distance, ox = params->ouverture_x, oy = params->ouverture_y;
-    double AO = params->AO_intensity;
-    if (params->compat_int_truncation && params->semantics != RT_SEM_CUDA) {   /* ThreadData int fields, main.c:42-43 */
-        focus = (double)(int)focus;
-        ox = (double)(int)ox;
-        oy = (double)(int)oy;
-        AO = (double)(int)AO;
-    }
-    int portable = g_math_mode >= 0 ? g_math_mode : (params->rng == RT_RNG_PHILOX);
+    band proto;
+    band_init(&proto, scene, params);
     if (params->rng == RT_RNG_GLIBC && reseed) srand(1);
 
     band* bands = (band*)calloc((size_t)nthreads, sizeof(band));
@@ -909,15 +931,9 @@ int oracle_render_rows(const rt_scene* scene, const rt_params* params, int row_h
         int end_row = start_row - rows_per_thread + 1;
         if (t == nthreads - 1) end_row -= remaining_rows;
         band* b = &bands[t];
-        b->sc = scene;
-        b->p = params;
+        *b = proto;
         b->start_row = start_row;
         b->end_row = end_row;
-        b->focus = focus;
-        b->ox = ox;
-        b->oy = oy;
-        b->AO = AO;
-        b->portable = portable;
         b->canva = canva;
         b->albedo = albedo;
         b->normal = normal;
@@ -935,6 +951,107 @@ int oracle_render_rows(const rt_scene* scene, const rt_params* params, int row_h
             for (int k = 0; k < RT_NCOUNTERS; k++) counters[k] += bands[t].cnt[k];
     }
     free(bands);
+    free(th);
+    return RT_OK;
+}
+
+/* ------------------------------------------------------------------------ */
+/* rt_accumulate_async, rt.h "progressive rendering"                          */
+/* ------------------------------------------------------------------------ */
+typedef struct acc_job {
+    band b;
+    const rt_tiling* t;
+    int ly0, ly1;                /* local rows [ly0, ly1) */
+    long long s_off;
+    double* sums;
+} acc_job;
+
+static void acc_add(double* a, const rt_color v[3])
+{
+    for (int k = 0; k < 3; k++) {
+        rt_color cur = v3(a[3 * k], a[3 * k + 1], a[3 * k + 2]);
+        cur = add(cur, v[k]);
+        a[3 * k] = cur.e[0];
+        a[3 * k + 1] = cur.e[1];
+        a[3 * k + 2] = cur.e[2];
+    }
+}
+
+static void* acc_worker(void* arg)
+{
+    acc_job* job = (acc_job*)arg;
+    const band* b = &job->b;
+    const rt_params* p = b->p;
+    const rt_tiling* t = job->t;
+    const int W = p->largeur_image, H = p->hauteur_image, S = p->nbRayonParPixel;
+    ctx c;
+    init_ctx(&c, b);
+    const int P = rt_resolve_spp_chunks(p->spp_chunks, S);
+    for (int ly = job->ly0; ly < job->ly1; ++ly) {
+        const int lt = ly / t->tile_rows, y = ly - lt * t->tile_rows;
+        const long long tile = (long long)t->tile_first + (long long)lt * t->tile_step;
+        const long long g = (long long)t->row_base + tile * t->tile_rows + y;
+        if (g >= H) continue;                                /* rt.h rt_tiling: rows >= H are skipped */
+        for (int i = 0; i < W; i++) {
+            const uint32_t pixel = (uint32_t)((int)g * W + i);
+            double* a = job->sums + ((long long)ly * W + i) * 9;
+            for (int ch = 0; ch < P; ++ch) {
+                const int s0 = (int)rt_chunk_bound(ch, S, P), s1 = (int)rt_chunk_bound(ch + 1, S, P);
+                double part[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+                double* fold = P == 1 ? a : part;            /* one slice: the running sums go on */
+                for (int x = s0; x < s1; ++x) {
+                    rt_color smp[3];
+                    trace_pixel_sample(&c, b, i, (int)g, pixel, (uint32_t)(job->s_off + x), smp);
+                    acc_add(fold, smp);
+                }
+                if (P > 1) {
+                    const rt_color pv[3] = {v3(part[0], part[1], part[2]), v3(part[3], part[4], part[5]),
+                                            v3(part[6], part[7], part[8])};
+                    acc_add(a, pv);
+                }
+            }
+        }
+    }
+    return NULL;
+}
+
+int oracle_accumulate(const rt_scene* scene, const rt_params* params, long long sample_offset,
+                      const rt_tiling* tiling, int nthreads, double* sums)
+{
+    int rc = validate(scene, params);
+    if (rc) return rc;
+    if (params->rng != RT_RNG_PHILOX) return RT_EINVAL;      /* the glibc stream has no sample key */
+    if (!tiling || !sums) return RT_EINVAL;
+    if (tiling->tile_rows < 1 || tiling->tile_step < 1 || tiling->n_tiles < 1 || tiling->tile_first < 0 ||
+        tiling->row_base < 0)
+        return RT_EINVAL;
+    if ((long long)tiling->n_tiles * tiling->tile_rows > (1ll << 30)) return RT_EINVAL;
+    if (sample_offset < 0 || sample_offset + params->nbRayonParPixel > (1ll << 32)) return RT_EINVAL;
+    const int rows = tiling->n_tiles * tiling->tile_rows;
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > rows) nthreads = rows;
+    acc_job* jobs = (acc_job*)calloc((size_t)nthreads, sizeof(acc_job));
+    pthread_t* th = (pthread_t*)calloc((size_t)nthreads, sizeof(pthread_t));
+    if (!jobs || !th) {
+        free(jobs);
+        free(th);
+        return RT_ENOMEM;
+    }
+    for (int k = 0; k < nthreads; k++) {
+        band_init(&jobs[k].b, scene, params);
+        jobs[k].t = tiling;
+        jobs[k].ly0 = (int)((long long)rows * k / nthreads);
+        jobs[k].ly1 = (int)((long long)rows * (k + 1) / nthreads);
+        jobs[k].s_off = sample_offset;
+        jobs[k].sums = sums;
+    }
+    if (nthreads == 1) {
+        acc_worker(&jobs[0]);
+    } else {
+        for (int k = 0; k < nthreads; k++) pthread_create(&th[k], NULL, acc_worker, &jobs[k]);
+        for (int k = 0; k < nthreads; k++) pthread_join(th[k], NULL);
+    }
+    free(jobs);
     free(th);
     return RT_OK;
 }

@@ -40,6 +40,25 @@ int oracle_render_rows(const rt_scene* scene, const rt_params* params,
                        rt_color* canva, rt_color* albedo, rt_color* normal,
                        rt_color* radiance, unsigned long long* counters);
 
+/* rt_accumulate_async (rt.h "progressive rendering") restated: adds samples
+ * [sample_offset, sample_offset + nbRayonParPixel) of every pixel of the
+ * tiling's local frame to sums (9 doubles per local pixel: radiance, albedo,
+ * normal; n_tiles*tile_rows*W entries, in/out).  Local row lt*tile_rows + y
+ * is global row g = row_base + (tile_first + lt*tile_step)*tile_rows + y; a
+ * row with g >= H is left untouched.  The stream of a sample is (seed,
+ * g*W + i, (uint32_t)(sample_offset + x)); camera draws, tracer and
+ * compat_int_truncation are oracle_render_rows'.  With P =
+ * rt_resolve_spp_chunks(spp_chunks, S): P == 1 continues the running sums in
+ * sample order; P > 1 folds each slice [rt_chunk_bound(c, S, P),
+ * rt_chunk_bound(c + 1, S, P)) of the batch's own S from (0, 0, 0) and adds
+ * the slice sums to the running sums in slice order.  RT_RNG_PHILOX only
+ * (the glibc stream has no sample key).  RT_EINVAL for a NULL tiling or sums,
+ * tile_rows, tile_step or n_tiles < 1, a negative row_base or tile_first, or
+ * a sample range outside [0, 2^32].  nthreads split the local rows; pixels
+ * are independent, so the result does not depend on it. */
+int oracle_accumulate(const rt_scene* scene, const rt_params* params, long long sample_offset,
+                      const rt_tiling* tiling, int nthreads, double* sums);
+
 /* Force the math library: -1 auto (libm for GLIBC, portable for PHILOX),
  * 0 libm, 1 portable.  Global; for experiments only. */
 void oracle_set_math(int mode);

@@ -1,12 +1,16 @@
 """What adaptive sampling's test files share: the float32 restatement of
 rt.h's selection pass (the thing rt_adaptive_select_async is specified by), the
-schedule of rt_adaptive_async, and the device drivers.  The references are the
-parent's rt_accumulate_async / rt_resolve_async and NumPy, never the new code."""
+schedule of rt_adaptive_async, each pixel's round count and sums by them, the
+device drivers and the glass scene.  The references are the parent's
+rt_accumulate_async / rt_resolve_async and NumPy, never the new code."""
 import ctypes as C
 
 import numpy as np
 
+import helpers
 import tipe_rt
+from gpu_driver import device_planes
+from tipe_rt import scenes
 from vdenoise_support import BLUR_G, D, F, lum2, shifted
 
 FLOOR = F(2.0 ** -8)
@@ -81,6 +85,33 @@ def schedule(first_half, max_rounds):
     for r in range(max_rounds):
         n = first_half << r
         out.append((0, n, n) if r == 0 else (n, n // 2, n))
+    return out
+
+
+# ---- rt_adaptive_async's reference, pixel by pixel -----------------------------------
+
+def reference_rounds(per_round, first_half, tolerance):
+    """Each pixel's round count by the restatement: (H, W) int32."""
+    R = len(per_round)
+    H, W = per_round[0][0].shape[:2]
+    state = Select(W, H)
+    rounds = np.zeros((H, W), dtype=np.int32)
+    active = None
+    for r in range(R - 1):
+        A, B = per_round[r]                      # an active pixel holds its (r + 1)-round sums
+        active = state(A, B, first_half << r, tolerance, r, active, rounds)
+    if R == 1:
+        rounds[:] = 1
+    else:
+        rounds.reshape(-1)[active.astype(np.int64)] = R
+    return rounds
+
+
+def pick(per_round, rounds, which):
+    """Pixel p from the accumulators of its own round count."""
+    out = np.empty_like(per_round[0][which])
+    for k in range(1, len(per_round) + 1):
+        out[rounds == k] = per_round[k - 1][which][rounds == k]
     return out
 
 
@@ -187,3 +218,27 @@ def sizeof_adaptive_params(tmp_path):
     subprocess.run(["gcc", "-std=c11", "-I", os.path.join(root, "include"), "-o", str(exe), str(src)], check=True)
     return int(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout), C.sizeof(
         tipe_rt.types.AdaptiveParams)
+
+
+def device_adaptive(ds, p, ap, frame=True):
+    """rt_adaptive_async on torch's current stream: (A, B, rounds, planes) as host arrays."""
+    import torch
+    W, H = p.largeur_image, p.hauteur_image
+    st = torch.cuda.current_stream().cuda_stream
+    acc = torch.full((2, H, W, 9), float("nan"), dtype=torch.float64, device="cuda:0")    # zeroed by the call
+    rounds = torch.full((H, W), -7, dtype=torch.int32, device="cuda:0")
+    nbytes = tipe_rt.lib().rt_adaptive_workspace_bytes(W, H)
+    ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device="cuda:0")
+    planes = device_planes(H, W)
+    tipe_rt.adaptive_async(ds, p, ap, acc[0].data_ptr(), acc[1].data_ptr(), rounds.data_ptr(), ws.data_ptr(), nbytes,
+                           *([t.data_ptr() for t in planes] if frame else []), stream=st)
+    torch.cuda.synchronize()
+    host = acc.cpu().numpy()
+    return host[0], host[1], rounds.cpu().numpy(), [t.cpu().numpy() for t in planes]
+
+
+GLASS = scenes.material((1.0, 1.0, 1.0), (0.0, 0.0, 0.0), 0.0, 0.0, 0.3, 1.5)
+
+
+def glass_cornell():
+    return helpers.cornell(extra=[((-0.3, -0.55, -1.9), 0.4, GLASS)])

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tipe-raytracer_amd"))
 
 from tipe_rt.types import (Vec3, Ray, Material, Sphere, Triangle, Camera, Scene,  # noqa: E402
-                           Params, RT_NCOUNTERS)
+                           Params, Tiling, RT_NCOUNTERS)
 
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_SO = os.path.join(ORACLE_DIR, "liboracle.so")
@@ -46,6 +46,8 @@ def oracle():
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            P(C.c_ulonglong)]
         lib.oracle_render_rows.restype = C.c_int
+        lib.oracle_accumulate.argtypes = [P(Scene), P(Params), C.c_longlong, P(Tiling), C.c_int, C.c_void_p]
+        lib.oracle_accumulate.restype = C.c_int
         lib.oracle_set_math.argtypes = [C.c_int]
         lib.oracle_set_mesh_cull.argtypes = [C.c_int]
         lib.oracle_hit_sphere.argtypes = [Vec3, C.c_double, Ray]

@@ -15,7 +15,7 @@ import pytest
 
 import helpers
 import tipe_rt
-from adaptive_support import Select, schedule, u64
+from adaptive_support import device_adaptive, glass_cornell, pick, reference_rounds, schedule, u64
 from gpu_driver import device_planes
 from tipe_rt import scenes
 from tipe_rt import types as T
@@ -23,11 +23,6 @@ from tipe_rt import types as T
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 40, 30
 BOUNCES = 5
-GLASS = scenes.material((1.0, 1.0, 1.0), (0.0, 0.0, 0.0), 0.0, 0.0, 0.3, 1.5)
-
-
-def glass_cornell():
-    return helpers.cornell(extra=[((-0.3, -0.55, -1.9), 0.4, GLASS)])
 
 
 def lamp_behind_the_camera():
@@ -68,46 +63,6 @@ def round_accumulators(ds, p, first_half, max_rounds):
         host = acc.cpu().numpy()
         out.append((host[0].copy(), host[1].copy()))
     return out
-
-
-def reference_rounds(per_round, first_half, tolerance):
-    """Each pixel's round count by the restatement: (H, W) int32."""
-    R = len(per_round)
-    state = Select(W, H)
-    rounds = np.zeros((H, W), dtype=np.int32)
-    active = None
-    for r in range(R - 1):
-        A, B = per_round[r]                      # an active pixel holds its (r + 1)-round sums
-        active = state(A, B, first_half << r, tolerance, r, active, rounds)
-    if R == 1:
-        rounds[:] = 1
-    else:
-        rounds.reshape(-1)[active.astype(np.int64)] = R
-    return rounds
-
-
-def pick(per_round, rounds, which):
-    """Pixel p from the accumulators of its own round count."""
-    out = np.empty_like(per_round[0][which])
-    for k in range(1, len(per_round) + 1):
-        out[rounds == k] = per_round[k - 1][which][rounds == k]
-    return out
-
-
-def device_adaptive(ds, p, ap, frame=True):
-    """rt_adaptive_async on torch's current stream: (A, B, rounds, planes) as host arrays."""
-    import torch
-    st = torch.cuda.current_stream().cuda_stream
-    acc = torch.full((2, H, W, 9), float("nan"), dtype=torch.float64, device="cuda:0")    # zeroed by the call
-    rounds = torch.full((H, W), -7, dtype=torch.int32, device="cuda:0")
-    nbytes = tipe_rt.lib().rt_adaptive_workspace_bytes(W, H)
-    ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device="cuda:0")
-    planes = device_planes(H, W)
-    tipe_rt.adaptive_async(ds, p, ap, acc[0].data_ptr(), acc[1].data_ptr(), rounds.data_ptr(), ws.data_ptr(), nbytes,
-                           *([t.data_ptr() for t in planes] if frame else []), stream=st)
-    torch.cuda.synchronize()
-    host = acc.cpu().numpy()
-    return host[0], host[1], rounds.cpu().numpy(), [t.cpu().numpy() for t in planes]
 
 
 def reference_planes(per_round, rounds, p, first_half):

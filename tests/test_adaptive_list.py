@@ -13,24 +13,9 @@ import pytest
 
 import helpers
 import tipe_rt
+from accumulate_support import SCENES
 from adaptive_support import accumulate_dense, accumulate_list, sentinel, u64
-from tipe_rt import scenes
 from tipe_rt.types import RT_EINVAL, RT_EUNSUPPORTED, RT_SPP_CHUNKS_AUTO
-
-SCENES = {
-    "cornell": (helpers.cornell, {}),                       # no tree: samples_flat
-    "pyramid": (helpers.pyramid_scene, {}),                 # brute-force triangles
-    "tree": (helpers.tree_scene, {}),                       # narrow tree: samples_coop
-    "sky": (helpers.sky_scene, dict(sky_mode=1)),
-    "sky_tree": (helpers.sky_tree_scene, dict(sky_mode=1)),
-    # 66 248 triangles (test_gpu_big_mesh's builder): a wide tree
-    "wide": (lambda: helpers.SceneBundle(scenes.cornell_spheres(),
-                                         scenes.heightfield_mesh(182, 1, 0.25, scenes.README_FLOOR, alpha=0.5)), {}),
-    "wide_sky": (lambda: helpers.SceneBundle(helpers.sky_scene().spheres,
-                                             scenes.heightfield_mesh(182, 1, 0.25, scenes.README_FLOOR, alpha=0.5),
-                                             sky=helpers.sky_scene().sky), dict(sky_mode=1)),
-}
-
 
 _UPLOADED = {}
 

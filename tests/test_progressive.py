@@ -10,6 +10,7 @@ import pytest
 
 import helpers
 import tipe_rt
+from accumulate_support import assert_same_sums, consecutive, device_batches, oracle_batches, whole
 from gpu_driver import assert_same, assert_same_frame, device_planes, gpu_render
 
 pytestmark = pytest.mark.gpu
@@ -62,6 +63,16 @@ def test_chunked_batches_are_deterministic():
         assert (x.view(np.uint64) == y.view(np.uint64)).all()
     one = gpu_render(bundle, p)
     assert (helpers.rmse_per_channel(a[3], one[3]) <= 1e-12).all()
+    # the raw sums against the oracle's restatement of the fold: each batch adds its own 3 slice sums in
+    # slice order (the slices of 4 and of 6 samples, not of the frame's 10) onto the running sums
+    batches = consecutive([(4, 3), (6, 3)])
+    zero = np.zeros((21, 33, 9))
+    ds = tipe_rt.DeviceScene(bundle.scene, 0)
+    sums, kernels = device_batches(ds, p, batches, whole(21), zero)
+    ds.close()
+    assert kernels == ["render_kernel"] * 2
+    assert_same_sums(sums, oracle_batches(bundle, p, batches, whole(21), zero), "raw sums")
+    assert (sums[..., 0:3] / 10 == a[3]).all() and sums[..., 6:9].any(axis=2).all()    # what `a` resolved
 
 
 def test_offset_beyond_32_bits_rejected():
