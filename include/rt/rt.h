@@ -366,7 +366,12 @@ enum {
     RT_CNT_CASTS,         /* closest-hit casts (bounce + AO)               */
     RT_CNT_SPHERE_TESTS,  /* ray-sphere tests                              */
     RT_CNT_SPHERE_DISC,   /* ... with discriminant > 0                     */
-    RT_CNT_TRI_TESTS,     /* ray-triangle tests                            */
+    RT_CNT_TRI_TESTS,     /* ray-triangle tests the reference makes: with
+                             RT_SEM_MAIN_C every cast tests all nbTriangles
+                             (main.c:81-90), whatever the BVH skips; with
+                             RT_SEM_CUDA only the casts that meet the mesh
+                             box test them (main_cuda.cu:40-45; triangle.hu's
+                             hit_BBox), the others count none          */
     RT_CNT_SHADE,         /* direction samples (random_dir_no_norm calls)  */
     RT_CNT_TEX_HITS,      /* closest hits on a triangle (texel fetch)      */
     RT_CNT_REFRACT,       /* refraction-branch events                      */
@@ -432,10 +437,21 @@ int rt_resolve_async(const double* d_sums, const rt_params* params, int total_sp
  * (a black-diffuse light, a green wall then a red one, an AO miss); those
  * bounces add exactly 0.  Render launches end such paths early when that is
  * provably exact for the scene and parameters (bounded materials, and with
- * AO 0 < AO_intensity <= 1000 and coordinates within 2^20), so frames are
- * bit-identical either way; only the work done, and so rt_count_async's
- * cast/shade/draw counts, differ.  Process-wide, default on; 0 reproduces
- * the reference's counts (tests).  Returns the previous setting. */
+ * AO 0 < AO_intensity <= 1000 and coordinates within 2^20; never with
+ * RT_SEM_CUDA), so frames are bit-identical either way; only the work done,
+ * and so rt_count_async's cast/shade/draw counts, differ.
+ * The rule: the path ends as soon as all three channels of rayColor compare
+ * == 0.0, tested in two places of a bounce that shades (main.c:208-234):
+ *  - after rayColor = diffuseColor * rayColor.  With AO this is before
+ *    ambient_occlusion: that bounce's AO direction is not drawn
+ *    (RT_CNT_SHADE, two of RT_CNT_RNG_DRAWS) and its AO cast is not made;
+ *  - after rayColor *= occlusion (an AO miss gives occlusion 0).
+ * The sample's incomingLight so far is added as usual.  rt_count_async counts
+ * exactly what the oracle's restatement of this rule counts
+ * (oracle_set_zero_exit, rt_oracle.h; tests/test_gpu_counters.py), and with
+ * the exit off what the reference's tracer does.
+ * Process-wide, default on; 0 reproduces the reference's counts (tests).
+ * Returns the previous setting. */
 int rt_set_zero_throughput_exit(int enable);
 
 /* ---- denoiser hook (denoiser.h:31-91, called at main.c:455) -------------- */

@@ -78,6 +78,7 @@ typedef struct ctx {
     int cuda;                /* rt.h RT_SEM_CUDA: main_cuda.cu's integrator */
     rt_point3 bb_lo, bb_hi;  /* CUDA mode: the triangles' bounding box */
     int mesh_cull;           /* main.c mode: skip the triangle scan for rays that miss mb_lo..mb_hi */
+    int zero_exit;           /* main.c mode: oracle_set_zero_exit, tracer leaves its loop at rayColor == 0 */
     rt_point3 mb_lo, mb_hi;  /* the triangles' box padded by 2^-16 (1 + max |coordinate|) */
     uint64_t seed;
     uint32_t pixel, sample, n;
@@ -541,6 +542,18 @@ static ind_ref info_pile_actuelle(pile* p)            /* pile.h:68-72 */
 /* ------------------------------------------------------------------------ */
 /* tracer, main.c:118-242                                                    */
 /* ------------------------------------------------------------------------ */
+/* rt.h's zero-throughput exit restated (not a reference behaviour: main.c
+ * never leaves early).  With the switch on, tracer leaves its bounce loop as
+ * soon as all three channels of rayColor compare == 0.0: after the bounce's
+ * rayColor = diffuseColor * rayColor -- with AO before ambient_occlusion, so
+ * that bounce's AO direction draw and cast do not happen -- or after
+ * rayColor *= occlusion.  Unconditional: the library's gates (bounded
+ * materials, the AO range) are what makes the exit exact, and the tests
+ * choose scenes on either side of them.  tracer_cuda ignores the switch. */
+static int g_zero_exit = 0;
+void oracle_set_zero_exit(int on) { g_zero_exit = on; }
+static inline int is_black(rt_color c) { return c.e[0] == 0.0 && c.e[1] == 0.0 && c.e[2] == 0.0; }
+
 static void tracer(ctx* c, rt_ray r, rt_color out[3])
 {
     rt_color incomingLight = v3(0, 0, 0);
@@ -627,14 +640,17 @@ static void tracer(ctx* c, rt_ray r, rt_color out[3])
                 if (rayColor.e[0] > 0.5 || rayColor.e[1] > 0.5 || rayColor.e[2] > 0.5)
                     rayColor = mul(mat.diffuseColor, mul_s(rayColor, 1.3));
                 rayColor = mul(mat.diffuseColor, rayColor);
+                if (c->zero_exit && is_black(rayColor)) break;
                 rt_color occlusion = ambient_occlusion(c, h.hitPoint, h.normal, c->AO);
                 rayColor = mul(rayColor, occlusion);
+                if (c->zero_exit && is_black(rayColor)) break;
             } else {                                                /* main.c:224-234 */
                 rt_color emittedLight = mul_s(mat.emissionColor, mat.emissionStrength);
                 incomingLight = add(incomingLight, mul(emittedLight, rayColor));
                 if (rayColor.e[0] > 0.5 || rayColor.e[1] > 0.5 || rayColor.e[2] > 0.5)
                     rayColor = mul(mat.diffuseColor, mul_s(rayColor, 1.3));
                 rayColor = mul(mat.diffuseColor, rayColor);
+                if (c->zero_exit && is_black(rayColor)) break;
             }
         } else {
             break;
@@ -757,6 +773,7 @@ static void init_ctx(ctx* c, const band* b)
     c->sky = b->p->sky_mode == RT_SKY_LAST_SPHERE && b->sc->sky_mat_list && b->sc->nbSpheres > 0;
     c->seed = b->p->seed;
     c->cuda = b->p->semantics == RT_SEM_CUDA;
+    c->zero_exit = g_zero_exit;
     if (!c->cuda && b->sc->nbTriangles > 0 && g_mesh_cull) {
         double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, m = 0.0;
         int finite = 1;

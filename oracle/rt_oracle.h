@@ -65,6 +65,18 @@ void oracle_set_math(int mode);
 /* Speed only: skip the triangle scan of rays that cannot meet the mesh's
  * padded box (main.c mode; default on, identical frames either way). */
 void oracle_set_mesh_cull(int on);
+/* rt.h's zero-throughput exit (rt_set_zero_throughput_exit) restated, so
+ * that rt_count_async has a reference with the exit on.  Process-wide,
+ * default off: the reference's tracer never leaves early.  With it on,
+ * tracer (main.c semantics only; RT_SEM_CUDA ignores it) leaves the bounce
+ * loop as soon as rayColor == (0, 0, 0) exactly, tested in two places: after
+ * the bounce's rayColor = diffuseColor * rayColor (with AO this is before
+ * ambient_occlusion: that bounce's AO draws and cast are not made), and after
+ * rayColor *= occlusion.  Unconditional -- the host's gates (rt.h) are not
+ * restated: inside them the planes equal the run that never exits byte for
+ * byte and only the counters fall (tests/test_oracle_zero_exit.py); outside
+ * them (an emission that overflows to inf, inf * 0 = NaN) the planes differ. */
+void oracle_set_zero_exit(int on);
 
 /* Leaf functions (for parity against the compiled reference headers). */
 oracle_hit oracle_hit_sphere(rt_point3 center, double radius, rt_ray r);

@@ -65,12 +65,16 @@ class Uploaded:
         self.kernel = tipe_rt.last_render_kernel()
         return [b.cpu().numpy() for b in bufs]
 
-    def counts(self, p):
-        """rt_count_async over the whole frame: the RT_NCOUNTERS event totals."""
+    def counts(self, p, tiling=None, into=None):
+        """rt_count_async over the tiling's rows (the whole frame by default):
+        the RT_NCOUNTERS event totals.  into: an int64 device tensor of
+        RT_NCOUNTERS entries the launch adds to (a fresh zeroed one by
+        default); its values after the launch are returned."""
         import torch
-        d = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device="cuda:0")
-        tipe_rt.count_async(self.ds, p, tipe_rt.band_tiling(0, p.hauteur_image - 1), d.data_ptr(),
-                            torch.cuda.current_stream().cuda_stream)
+        if tiling is None:
+            tiling = tipe_rt.band_tiling(0, p.hauteur_image - 1)
+        d = torch.zeros(tipe_rt.RT_NCOUNTERS, dtype=torch.int64, device="cuda:0") if into is None else into
+        tipe_rt.count_async(self.ds, p, tiling, d.data_ptr(), torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         return [int(x) for x in d.cpu()]
 

@@ -146,15 +146,21 @@ def params(W, H, spp, bounces, use_ao=False, ao=2.5, rng=RT_RNG_PHILOX, seed=101
                                semantics=semantics)
 
 
-def oracle_render(bundle, p, row_hi=None, row_lo=0, nthreads=1, counters=False):
+def oracle_render(bundle, p, row_hi=None, row_lo=0, nthreads=1, counters=False, zero_exit=False):
+    """zero_exit: the oracle's restatement of the zero-throughput exit
+    (rt_oracle.h oracle_set_zero_exit) for this call; off again afterwards."""
     W, H = p.largeur_image, p.hauteur_image
     if row_hi is None:
         row_hi = H - 1
     canva, alb, nrm, rad = (np.zeros((H, W, 3)) for _ in range(4))
     cnt = oracle_ffi.counters() if counters else None
-    rc = oracle_ffi.oracle().oracle_render_rows(C.byref(bundle.scene), C.byref(p), row_hi, row_lo, nthreads, 1,
-                                                canva.ctypes.data, alb.ctypes.data, nrm.ctypes.data,
-                                                rad.ctypes.data, cnt)
+    lib = oracle_ffi.oracle()
+    lib.oracle_set_zero_exit(1 if zero_exit else 0)
+    try:
+        rc = lib.oracle_render_rows(C.byref(bundle.scene), C.byref(p), row_hi, row_lo, nthreads, 1,
+                                    canva.ctypes.data, alb.ctypes.data, nrm.ctypes.data, rad.ctypes.data, cnt)
+    finally:
+        lib.oracle_set_zero_exit(0)
     assert rc == 0, rc
     out = dict(canva=canva, albedo=alb, normal=nrm, radiance=rad)
     if counters:

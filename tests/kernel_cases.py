@@ -3,6 +3,8 @@ picks for a scene, as data.  The GPU tests render each scene and assert
 rt_last_render_kernel's name; tests/test_launch_plan.py checks the same
 triples on the CPU.  Nothing here touches the device.
 """
+import functools
+
 import helpers
 from tipe_rt import scenes
 from tipe_rt.types import Material
@@ -118,5 +120,14 @@ FALLBACK = {
     "shallow_far": (shallow_far_scene, lambda: helpers.params(48, 36, 8, 6, chunks=4), "render_kernel_q<QB=4>"),
 }
 
-# ---- wide trees (tests/test_gpu_big_mesh.py) -----------------------------------
+# ---- wide trees (tests/test_gpu_big_mesh.py, test_gpu_counters.py, test_cuda_semantics.py) ----
 QB5, BVH32 = "render_kernel_q<QB=5>", "render_kernel<BVH32>"
+
+
+@functools.lru_cache(maxsize=None)
+def alpha_mesh():
+    """66 248 triangles (above 65535: a wide tree) with a refracting (alpha
+    0.5) texel and an alpha-0 hole, as the README box's floor.  Built once
+    per process and shared: callers that change it take a copy
+    (helpers.mesh_of)."""
+    return scenes.heightfield_mesh(182, 1, 0.25, scenes.README_FLOOR, alpha=0.5)

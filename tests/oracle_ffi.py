@@ -50,6 +50,7 @@ def oracle():
         lib.oracle_accumulate.restype = C.c_int
         lib.oracle_set_math.argtypes = [C.c_int]
         lib.oracle_set_mesh_cull.argtypes = [C.c_int]
+        lib.oracle_set_zero_exit.argtypes = [C.c_int]
         lib.oracle_hit_sphere.argtypes = [Vec3, C.c_double, Ray]
         lib.oracle_hit_sphere.restype = OracleHit
         lib.oracle_hit_sphere_cuda.argtypes = [Vec3, C.c_double, Ray]

@@ -152,15 +152,58 @@ def test_gpu_cuda_mode_tree_bvh_bitexact():
     check_parity(bundle, helpers.params(24, 18, 4, 6, use_ao=True, ao=3.0, semantics=RT_SEM_CUDA))
 
 
+def _cuda_pyramid():
+    return helpers.SceneBundle(scenes.cornell_spheres(), scenes.with_cuda_materials(scenes.pyramid_mesh()))
+
+
+def _cuda_tree():
+    return helpers.SceneBundle(scenes.cornell_spheres(), scenes.with_cuda_materials(scenes.tree_mesh()))
+
+
+def _cuda_wide():
+    import kernel_cases
+    mesh = kernel_cases.alpha_mesh()                    # shared: the triangles' own materials go on a copy
+    return helpers.SceneBundle(scenes.cornell_spheres(), scenes.with_cuda_materials(helpers.mesh_of(mesh, len(mesh[0]))))
+
+
+def assert_cuda_counters_match_oracle(bundle, p, bvh, nthreads=1):
+    """The nine reference counters (RT_CNT_SAMPLES .. RT_CNT_RNG_DRAWS) of
+    render_kernel_cuda<COUNT> against the oracle's tracer_cuda, exactly.
+    RT_CNT_TRI_TESTS is main_cuda.cu:40-45's: the triangles are tested only by
+    casts that meet the mesh box.  Texture hits are a main.c event
+    (tri_uvmapping); CUDA mode has none."""
+    from gpu_driver import gpu_counts
+    T = tipe_rt.types
+    ref = helpers.oracle_render(bundle, p, nthreads=nthreads, counters=True)["counters"]
+    got = gpu_counts(bundle, p)
+    nine = T.RT_CNT_EXACT_RESCANS
+    names = tipe_rt.COUNTER_NAMES
+    print(dict(zip(names, got)))
+    assert [int(x) for x in got[:nine]] == [int(x) for x in ref[:nine]], (dict(zip(names, got)),
+                                                                          dict(zip(names, (int(x) for x in ref))))
+    nt = bundle.scene.nbTriangles
+    assert got[T.RT_CNT_TEX_HITS] == 0 and got[T.RT_CNT_REFRACT] == 0
+    # some casts miss the mesh box and some meet it: the count is neither 0 nor main.c's casts x triangles
+    assert 0 < got[T.RT_CNT_TRI_TESTS] < got[T.RT_CNT_CASTS] * nt and got[T.RT_CNT_TRI_TESTS] % nt == 0
+    assert got[T.RT_CNT_BVH_TRI_TESTS] <= got[T.RT_CNT_TRI_TESTS]
+    assert (got[T.RT_CNT_BVH_NODES] > 0) == bvh and got[T.RT_CNT_BVH_STACK_OVER] == 0
+
+
 @pytest.mark.gpu
 def test_gpu_cuda_mode_counters_match_oracle():
-    from gpu_driver import gpu_counts
-    mesh = scenes.with_cuda_materials(scenes.pyramid_mesh())
-    bundle = helpers.SceneBundle(scenes.cornell_spheres(), mesh)
-    p = helpers.params(24, 18, 4, 6, use_ao=True, ao=2.5, semantics=RT_SEM_CUDA)
-    ref = helpers.oracle_render(bundle, p, counters=True)["counters"]
-    got = gpu_counts(bundle, p)
-    # texture hits are a main.c event (tri_uvmapping); CUDA mode has none
-    for k in (tipe_rt.types.RT_CNT_SAMPLES, tipe_rt.types.RT_CNT_CASTS, tipe_rt.types.RT_CNT_SPHERE_TESTS,
-              tipe_rt.types.RT_CNT_SPHERE_DISC, tipe_rt.types.RT_CNT_SHADE, tipe_rt.types.RT_CNT_RNG_DRAWS):
-        assert got[k] == ref[k], (tipe_rt.COUNTER_NAMES[k], got[k], ref[k])
+    assert_cuda_counters_match_oracle(_cuda_pyramid(), helpers.params(24, 18, 4, 6, use_ao=True, ao=2.5,
+                                                                       semantics=RT_SEM_CUDA), bvh=False)
+
+
+@pytest.mark.gpu
+def test_gpu_cuda_mode_counters_match_oracle_bvh():
+    """render_kernel_cuda<COUNT, BVH>: the tree; 21x13 leaves partial waves and blocks."""
+    assert_cuda_counters_match_oracle(_cuda_tree(), helpers.params(21, 13, 3, 5, use_ao=True, ao=2.5,
+                                                                    semantics=RT_SEM_CUDA), bvh=True)
+
+
+@pytest.mark.gpu
+def test_gpu_cuda_mode_counters_match_oracle_wide():
+    """render_kernel_cuda_w<COUNT>: the 66 248-triangle mesh (a wide tree)."""
+    assert_cuda_counters_match_oracle(_cuda_wide(), helpers.params(16, 12, 2, 2, semantics=RT_SEM_CUDA), bvh=True,
+                                      nthreads=8)

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import helpers
+import kernel_cases
 import tipe_rt
 from gpu_driver import Uploaded, assert_same_frame
 from kernel_cases import QB5, BVH32
@@ -53,8 +54,9 @@ def big():
 
 @pytest.fixture(scope="module")
 def alpha_mesh():
-    """66 248 triangles with a refracting (alpha 0.5) texel and an alpha-0 hole."""
-    return scenes.heightfield_mesh(182, 1, 0.25, scenes.README_FLOOR, alpha=0.5)
+    """66 248 triangles with a refracting (alpha 0.5) texel and an alpha-0 hole
+    (kernel_cases.alpha_mesh: shared with the counter tests)."""
+    return kernel_cases.alpha_mesh()
 
 
 @pytest.fixture(scope="module")

@@ -304,19 +304,17 @@ struct LanePath {
                         inc = inc + mulv(em, r);
                         if (any_above_half(r)) r = mulv(mat.diff, muls(r, 1.3));
                         rc = mulv(mat.diff, r);
-                        // ambient_occlusion's cast (main.c:96-103): from hp along n + random
-                        cd = normalize(hn + random_dir<COUNT>(st, cnt));
-                        ao_cast = true;
+                        // ambient_occlusion's cast (main.c:96-103): from hp along n + random;
+                        // with rayColor black it could only scale 0: neither drawn nor cast
+                        ao_cast = !zero_rc(kp);
+                        if (ao_cast) cd = normalize(hn + random_dir<COUNT>(st, cnt));
                     } else {
                         const V3 em = muls(mat.emis, mat.es);
                         inc = inc + mulv(em, r);
                         if (any_above_half(r)) r = mulv(mat.diff, muls(r, 1.3));
                         rc = mulv(mat.diff, r);
                     }
-                    if (zero_rc(kp)) {           // black diffuse (a light, a green-then-red wall)
-                        ao_cast = false;         // the AO cast could only scale 0
-                        more = false;
-                    }
+                    if (zero_rc(kp)) more = false;   // black diffuse (a light, a green-then-red wall)
                 }
             }
         }

@@ -581,6 +581,8 @@ __device__ __forceinline__ int closest_hit(const KParams& kp, const V3 o, const 
     int win_orig = 0;
     if (CU && kp.nt > 0 && !cuda_bbox(kp, o, d)) {
         // main_cuda.cu:40-45: the ray misses the mesh box, no triangle tested
+        // (cast_spheres counted main.c's every-triangle scan: taken back)
+        if (COUNT) cnt.c[RT_CNT_TRI_TESTS] -= (unsigned long long)kp.nt;
     } else if (BVH) {
         tris_bvh<COUNT, CU, SE>(kp, o, d, best, kind, win, win_orig, cnt);
     } else if (!COUNT && !kp.tri_orig) {
