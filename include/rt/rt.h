@@ -51,7 +51,9 @@ extern "C" {
  *    rt_adaptive_async, rt_resolve_adaptive_async, rt_render_adaptive);
  *    the variance-guided denoiser with each pixel's own sample count, which
  *    filters an adaptive result (rt_vdenoise_adaptive_async,
- *    rt_render_adaptive_vdenoised).
+ *    rt_render_adaptive_vdenoised); the task-queue kernel for launches with
+ *    running sums, behind a switch (rt_set_accumulate_queue,
+ *    rt_last_list_kernel).
  * A caller compares rt_abi_version() with the RT_ABI_VERSION it was built
  * against before passing rt_params or counter arrays.                   */
 #define RT_ABI_VERSION 5
@@ -246,6 +248,16 @@ int rt_abi_version(void);
  * "render_kernel<BVH32>" = the fixed-grid one); "none" before the first.
  * The choice never changes a result.  Diagnostics and tests. */
 const char* rt_last_render_kernel(void);
+/* Name of the render kernel the calling thread's last list launch
+ * (rt_accumulate_list_async, and so every round after the first of
+ * rt_adaptive_async) used; list launches do not report through
+ * rt_last_render_kernel.  "render_kernel_list", "render_kernel_list<BVH>" or
+ * "render_kernel_list_w" (a wide tree) = the fixed-grid list kernels;
+ * "render_kernel_ql<QB=...>" = the task-queue list kernel of the pair that
+ * rt_last_render_kernel names as "render_kernel_q<QB=...>"
+ * (rt_set_accumulate_queue); "none" before the first.  The choice never
+ * changes a result.  Diagnostics and tests. */
+const char* rt_last_list_kernel(void);
 const char* rt_version(void);
 int  rt_device_count(void);
 
@@ -453,6 +465,24 @@ int rt_resolve_async(const double* d_sums, const rt_params* params, int total_sp
  * Process-wide, default on; 0 reproduces the reference's counts (tests).
  * Returns the previous setting. */
 int rt_set_zero_throughput_exit(int enable);
+
+/* Launches with running sums -- rt_accumulate_async, rt_accumulate_list_async
+ * and everything built on them (rt_adaptive_async, rt_render_vdenoised,
+ * rt_render_adaptive, rt_render_adaptive_vdenoised) -- take the fixed-grid
+ * kernels by default.  With this switch on they take the task-queue kernel
+ * wherever a render launch of the same scene and parameters would: the same
+ * (QB, OPQ) pair, stack and row bands for rt_accumulate_async
+ * (rt_last_render_kernel names it), "render_kernel_ql" of that pair for a
+ * list (rt_last_list_kernel).  A slice partial starts at +0.0 and takes its
+ * samples in order on either kernel, and the partials are added to the running
+ * sums in slice order, so every sum is bit-identical either way.  These
+ * launches keep the fixed grid with the switch on: one sample slice
+ * (spp_chunks resolving to 1, which continues the sums in sample order),
+ * RT_SEM_CUDA, a tree that no queue walk admits, and a band whose tasks
+ * (slices x pixels) reach 2^31.
+ * Process-wide and atomic, default off; read when a launch is enqueued.
+ * Returns the previous setting. */
+int rt_set_accumulate_queue(int enable);
 
 /* ---- denoiser hook (denoiser.h:31-91, called at main.c:455) -------------- */
 /* denoiser()'s signature.  main.c runs it once on the finished frame when

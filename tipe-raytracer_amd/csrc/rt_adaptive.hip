@@ -123,9 +123,16 @@ int launch_render_list(const KParams& kp, const RenderPlan& pl, const ListArgs& 
                               : (pl.sky ? K(render_kernel_list<false, true>) : K(render_kernel_list<false, false>));
     const unsigned blocks = (la.e1 - la.e0 + 255u) / 256u;
     hipLaunchKernelGGL(kernel, dim3(blocks, 1, (unsigned)kp.chunks), dim3(256), 0, (hipStream_t)stream, kp, la);
-    if (kp.chunks > 1)
-        hipLaunchKernelGGL(combine_list_kernel, dim3(std::min(blocks, 8192u)), dim3(256), 0, (hipStream_t)stream, la,
-                           kp.sums, kp.chunks, (unsigned)kp.W * (unsigned)kp.H);
+    if (kp.chunks > 1) return launch_combine_list(kp, la, stream);
+    return (int)hipGetLastError();
+}
+
+// The band's combine, for either render kernel (rt_queue_list.hip writes the same partials).
+int launch_combine_list(const KParams& kp, const ListArgs& la, void* stream)
+{
+    const unsigned blocks = (la.e1 - la.e0 + 255u) / 256u;
+    hipLaunchKernelGGL(combine_list_kernel, dim3(std::min(blocks, 8192u)), dim3(256), 0, (hipStream_t)stream, la,
+                       kp.sums, kp.chunks, (unsigned)kp.W * (unsigned)kp.H);
     return (int)hipGetLastError();
 }
 

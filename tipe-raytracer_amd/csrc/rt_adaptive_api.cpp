@@ -8,6 +8,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
+#include <vector>
 
 #include "rt_host_slots.h"
 
@@ -92,6 +94,25 @@ AdaptiveSelect select_args(int W, int H, void* workspace)
     return s;
 }
 
+// rt_last_list_kernel: the render kernel of the calling thread's last list launch.
+thread_local const char* t_last_list = "none";
+
+// render_kernel_ql's name for the plan's pair: the pair's render_kernel_q name
+// (rt_queue_variants.h) with the kernel's own name in front.
+const char* list_queue_name(const RenderPlan& plan)
+{
+    static const std::vector<std::string> names = [] {
+        std::vector<std::string> n;
+        for (const QueueVariant& v : kQueueVariants) {
+            const char* args = std::strchr(v.name, '<');
+            n.push_back(std::string("render_kernel_ql") + (args ? args : ""));
+        }
+        return n;
+    }();
+    const int i = queue_variant_index(plan.qb, plan.opq);
+    return i < 0 ? "none" : names[(size_t)i].c_str();
+}
+
 // Every band of a list launch as plan_list (rt_launch_plan.cpp) sizes them, with
 // its stream-ordered scratch (the uniform block and, for chunks > 1, one band's
 // partials, reused band after band).
@@ -100,24 +121,35 @@ int launch_list_on_stream(KParams& kp, const double* uni, const unsigned* d_list
 {
     const int rc = keep_pool_memory();
     if (rc) return rc;
-    const RenderPlan plan = plan_render(kp, false);     // tree, width and sky (running sums: never the queue)
+    // tree, width and sky -- and, with rt_set_accumulate_queue on, whether a render launch of kp takes the
+    // queue and with which pair: the list then takes render_kernel_ql of that pair (chunks > 1: task_ok)
+    const RenderPlan plan = plan_render(kp, false);
     const ListPlan bands = plan_list(kp.chunks, list_cap);
     const unsigned band = bands.band;
     const size_t partial_bytes = bands.partial_bytes;
+    const bool queue = plan.queue && partial_bytes != 0;
+    t_last_list = queue ? list_queue_name(plan) : plan.wide ? "render_kernel_list_w"
+                                              : plan.bvh    ? "render_kernel_list<BVH>"
+                                                            : "render_kernel_list";
     double* d_uni = nullptr;
     double* d_part = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&d_uni, U_COUNT * sizeof(double), st));
+    // uniform block; for the queue, its task counter on a 64-byte line of its own and the band's task words
+    // on the next (launch_on_stream's layout, rt_internal.h kListTaskOffset)
+    constexpr int kCtr = ((U_COUNT + 7) / 8 + 1) * 8;
+    const size_t words = queue ? (kCtr * sizeof(double) + (kListTaskOffset + kListTaskWords) * sizeof(unsigned) + 7) / 8 : 0;
+    HIP_TRY(hipMallocAsync((void**)&d_uni, std::max<size_t>(U_COUNT, words) * sizeof(double), st));
     UniBlock ub;
     for (int i = 0; i < U_COUNT; ++i) ub.v[i] = uni[i];
     hipError_t e = (hipError_t)launch_set_uniforms(ub, d_uni, st);
     if (partial_bytes && e == hipSuccess) e = hipMallocAsync((void**)&d_part, partial_bytes, st);
     kp.uni = d_uni;
+    kp.task_ctr = queue ? (unsigned*)(d_uni + kCtr) : nullptr;
     kp.stack_cap = plan.stack_cap;
     ListArgs la = {d_list, d_count, d_part, 0u, 0u, band};
     for (unsigned long long e0 = 0; e == hipSuccess && e0 < list_cap; e0 += band) {
         la.e0 = (unsigned)e0;
         la.e1 = (unsigned)std::min<unsigned long long>(e0 + band, list_cap);
-        e = (hipError_t)launch_render_list(kp, plan, la, st);
+        e = (hipError_t)(queue ? launch_render_list_queue(kp, plan, la, st) : launch_render_list(kp, plan, la, st));
     }
     if (d_part) (void)hipFreeAsync(d_part, st);
     (void)hipFreeAsync(d_uni, st);
@@ -216,6 +248,8 @@ int rt_accumulate_list_async(const rt_device_scene* scene, const rt_params* para
     DeviceGuard guard(scene->device);
     return launch_list_on_stream(kp, uni, d_list, d_count, list_cap, (hipStream_t)hip_stream);
 }
+
+const char* rt_last_list_kernel(void) { return t_last_list; }
 
 size_t rt_adaptive_workspace_bytes(int W, int H)
 {

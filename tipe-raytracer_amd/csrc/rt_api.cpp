@@ -27,6 +27,7 @@ std::vector<int> g_devices;
 bool g_inited = false;
 
 std::atomic<int> g_zero_exit{1};
+std::atomic<int> g_acc_queue{0};     // rt_set_accumulate_queue
 
 int validate_tiling(const rt_tiling* t)
 {
@@ -142,6 +143,7 @@ void free_scene(rt_device_scene* s)
 void fill_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling* t, KParams& kp, double* uni)
 {
     fill_kparams(*sc, sc->facts, p, t, g_zero_exit.load() != 0, kp, uni);
+    kp.acc_queue = g_acc_queue.load();           // read by plan_render, and only for a launch with running sums
 }
 
 // The current device's default memory pool keeps freed blocks (release
@@ -282,6 +284,7 @@ int rt_device_count(void)
 }
 
 int rt_set_zero_throughput_exit(int enable) { return g_zero_exit.exchange(enable ? 1 : 0); }
+int rt_set_accumulate_queue(int enable) { return g_acc_queue.exchange(enable ? 1 : 0); }
 
 int rt_scene_upload(int device, const rt_scene* scene, rt_device_scene** out)
 {

@@ -152,6 +152,8 @@ struct KParams {
     unsigned npx_here;       // render_kernel_q: pixels of this band that exist (tasks = npx_here * chunks)
     unsigned qm_npx, qm_w, qm_tile, qm_chunks;   // floor((2^32-1)/d) for d = npx_here, W, tile_rows,
                                                  // chunks (udiv_q); qm_chunks 0: 64-bit chunk starts
+    int acc_queue;           // host only (plan_render): rt_set_accumulate_queue's switch -- a launch with running
+                             // sums may take the queue kernel.  (In the padding before trace: no field moves.)
     unsigned long long* trace;   // render_kernel_q diagnostics (RT_QUEUE_TRACE), normally null
     unsigned long long* counters;
     int opaque;              // host only (plan_render: QB -2): every sphere material opaque, !(alpha < 0.0001)
@@ -224,6 +226,14 @@ struct ListArgs {
     unsigned stride;         // entries of one chunk's plane of partial (the band size)
 };
 int launch_render_list(const KParams& kp, const RenderPlan& plan, const ListArgs& la, void* stream);
+// launcher (rt_queue_list.hip): the same band on the task-queue kernel render_kernel_ql<plan.qb, plan.opq, ...>
+// (plan.queue; chunks > 1), then combine_list_kernel.  kp.task_ctr: the launch's task counter, with
+// kListTaskWords launch-private words kListTaskOffset words behind it (the band's task count, entry count and
+// division magic, which a prologue kernel derives from the device's count word).
+constexpr int kListTaskOffset = 16, kListTaskWords = 3;
+int launch_render_list_queue(const KParams& kp, const RenderPlan& plan, const ListArgs& la, void* stream);
+// combine_list_kernel (rt_adaptive.hip) for one band, as launch_render_list ends with it.
+int launch_combine_list(const KParams& kp, const ListArgs& la, void* stream);
 // One selection pass (rt_adaptive_select_async) or one marking of the active
 // pixels' round counts, as their kernels' by-value argument.
 struct AdaptiveSelect {

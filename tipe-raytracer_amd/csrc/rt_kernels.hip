@@ -81,6 +81,7 @@
 #include "rt_shading.h"
 #include "rt_fixed_grid.h"
 #include "rt_queue.h"
+#include "rt_queue_launch.h"
 
 namespace rt {
 
@@ -280,66 +281,11 @@ static void launch_variant(const KParams& kp, const RenderPlan& pl, void* stream
     hipLaunchKernelGGL(kernel, grid_for(kp), dim3(256), 0, (hipStream_t)stream, kp);
 }
 
-// The 28 render_kernel_q instantiations: rt_queue_variants.h's (QB, OPQ) pairs
-// x sky x AO.  with_queue_variant maps the plan's tuple to its QVariant
-// (rt_queue.h) and hands it to f, so the kernel pointer and its occupancy cache
-// cannot disagree; false (f not called) when the pair is not in the list.  (A
-// row's kernels are named before the next row is looked at: the code object
-// holds the kernels in the table's order.)
+// render_kernel_q's instantiations are picked by rt_queue_launch.h's table walk
+// (with_queue_variant), which hands the plan's QVariant to queue_kernel.
 using QueueKernel = void (*)(const KParams);
 template <class V>
 constexpr QueueKernel queue_kernel(V) { return render_kernel_q<V::SKY, V::AOM, V::QB, V::OPQ>; }
-template <int QB, bool OPQ, class F>
-static void with_queue_variant_qb(const RenderPlan& pl, F&& f)
-{
-    if (pl.sky && pl.ao) f(QVariant<true, AO_ON, QB, OPQ>{});
-    else if (pl.sky) f(QVariant<true, AO_OFF, QB, OPQ>{});
-    else if (pl.ao) f(QVariant<false, AO_ON, QB, OPQ>{});
-    else f(QVariant<false, AO_OFF, QB, OPQ>{});
-}
-template <int I = 0, class F>
-static bool with_queue_variant(const RenderPlan& pl, F&& f)
-{
-    if constexpr (I < kQueueVariantCount) {
-        constexpr QueueVariant v = kQueueVariants[I];
-        if (pl.qb == v.qb && pl.opq == v.opq) {
-            with_queue_variant_qb<v.qb, v.opq>(pl, f);
-            return true;
-        }
-        return with_queue_variant<I + 1>(pl, f);
-    } else {
-        return false;
-    }
-}
-
-// Resident blocks of the queue kernel on this device (grid of render_kernel_q).
-// Cached per device and variant (one table per QVariant); rt_fill_canva may run
-// on several host threads at once (main.c's pthreads), so the cache is atomic
-// (every thread computes the same value).
-template <class V>
-static unsigned queue_grid(V)
-{
-    static std::atomic<int> cached[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::atomic<int>& slot = cached[dev & 63];
-    int c = slot.load(std::memory_order_relaxed);
-    if (c <= 0) {
-        int nb = 0, ncu = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, queue_kernel(V{}), 256, 0);
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        c = std::max(1, nb) * std::max(1, ncu);
-        if (std::getenv("RT_QUEUE_VERBOSE")) std::fprintf(stderr, "render_kernel_q: %d blocks/CU x %d CUs -> %d\n", nb, ncu, c);
-        slot.store(c, std::memory_order_relaxed);
-    }
-    // RT_QUEUE_BLOCKS (tests, experiments) is read on every launch, so a test
-    // can shrink the grid to a few blocks and give every lane hundreds of tasks.
-    if (const char* e = std::getenv("RT_QUEUE_BLOCKS")) c = std::max(1, std::atoi(e));
-    return (unsigned)c;
-}
-
-// floor((2^32 - 1) / d) for udiv_q
-static unsigned qdiv_magic(unsigned d) { return d ? (unsigned)(0xffffffffull / d) : 0u; }
 
 static thread_local const char* t_last_kernel = "none";
 const char* last_render_kernel() { return t_last_kernel; }
@@ -354,7 +300,7 @@ int launch_render(const KParams& kp, const RenderPlan& pl, void* stream)
         unsigned nb = 0;
         const bool listed = with_queue_variant(pl, [&](auto v) {
             kernel = queue_kernel(v);
-            nb = queue_grid(v);
+            nb = queue_grid(v, kernel, "render_kernel_q");
         });
         if (!listed) return (int)hipErrorInvalidValue;       // a (qb, opq) that plan_render cannot give
         (void)hipMemsetAsync(kp.task_ctr, 0, sizeof(unsigned), st);
@@ -366,11 +312,8 @@ int launch_render(const KParams& kp, const RenderPlan& pl, void* stream)
         const int rows_here = std::max(0, std::min(kp.band_rows, kp.local_rows - kp.band_y0));
         k2.npx_here = (unsigned)rows_here * (unsigned)kp.W;
         k2.qm_npx = qdiv_magic(k2.npx_here);
-        k2.qm_w = qdiv_magic((unsigned)kp.W);
         k2.qm_tile = qdiv_magic((unsigned)kp.tile_rows);
-        // chunk starts c*S/P in 32 bits when (P + 1) * S fits
-        k2.qm_chunks = (unsigned long long)(kp.chunk_den + 1) * (unsigned long long)kp.S < (1ull << 32)
-                           ? qdiv_magic(kp.chunk_den) : 0u;
+        set_queue_magics(k2);
         hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, st, k2);
         if (tr) {
             std::vector<unsigned long long> h((size_t)nb * 256 * RT_TRACE_WORDS);

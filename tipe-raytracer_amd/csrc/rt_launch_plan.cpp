@@ -129,9 +129,15 @@ void set_tiling(KParams& kp, const rt_tiling* t, int H)
 //    16 rows, at least 16, that reuse one buffer (pixels are independent, so
 //    banding changes no result).  A count run is one band without partials.
 //  * Queue or fixed grid.  render_kernel_q needs its task counter (task_ok: the
-//    render band's chunks * pixels below 2^31), RT_SEM_MAIN_C, no running sums
-//    and, with a BVH, a walk that admits the tree; every other launch takes the
-//    fixed grid (kStack4 entries).
+//    render band's chunks * pixels below 2^31), RT_SEM_MAIN_C and, with a BVH, a
+//    walk that admits the tree; every other launch takes the fixed grid (kStack4
+//    entries).  A launch with running sums (rt_accumulate_async) takes the fixed
+//    grid too unless kp.acc_queue (rt_set_accumulate_queue) is set; with it, the
+//    rules, the pair, the stack and the bands are a render launch's, and
+//    combine_kernel adds the slice partials to the sums in slice order.  One
+//    slice (chunks 1) never has a task counter: it carries the sums through the
+//    samples on the fixed grid.  A list launch (rt_accumulate_list_async) takes
+//    render_kernel_ql of the same pair when this plan says queue.
 //  * Which queue kernel: one of rt_queue_variants.h's kQueueVariants, which says
 //    what each (QB, OPQ) pair walks, its stack and whether it has the far-origin
 //    margins.  The rules here admit a scene to a pair.
@@ -167,7 +173,7 @@ RenderPlan plan_render(const KParams& kp, bool count)
     pl.bvh = kp.bvh != nullptr;
     pl.wide = pl.bvh && kp.bvh_wide;
     pl.stack_cap = pl.bvh ? kStack4 : 0;
-    const bool can_queue = pl.task_ok && !pl.cuda && !kp.sums;
+    const bool can_queue = pl.task_ok && !pl.cuda && (!kp.sums || kp.acc_queue);
     if (pl.wide) {
         if (can_queue && kp.bvhw != nullptr && kp.bvh_stack <= kStackQW) {
             pl.queue = true;

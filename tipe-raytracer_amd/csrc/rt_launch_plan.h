@@ -103,8 +103,9 @@ struct RenderPlan {
 RenderPlan plan_render(const KParams& kp, bool count);
 
 // The entry bands of a list launch (rt_accumulate_list_async) of up to list_cap
-// entries with `chunks` sample slices; launch_render_list (rt_adaptive.hip) runs
-// one band.
+// entries with `chunks` sample slices; launch_render_list (rt_adaptive.hip) or,
+// when plan_render gives the launch the queue, launch_render_list_queue
+// (rt_queue_list.hip) runs one band.
 struct ListPlan {
     unsigned band;           // entries per launch; the partials are per band (chunks 1: one band, no partials)
     size_t partial_bytes;    // chunk partials of one band, [chunks][band][9] doubles (0: none)

@@ -7,6 +7,7 @@
  *   rt_demo [-w W] [-s spp] [-b nbRebondMax] [-ao AO_intensity] [-o out.ppm]
  *           [-obj file.obj -mtl file.mtl [-move x y z]] [-devices N]
  *           [-denoise [iterations]] [-vdenoise [iterations]] [-adaptive TOL]
+ *           [-queue]
  *
  * -denoise installs the library's built-in a-trous filter (rt_denoise_atrous;
  * not OIDN, and biased: meant for low-spp frames) as the denoiser hook before
@@ -18,6 +19,8 @@
  * mean samples per pixel and the share of pixels per round count.
  * -adaptive with -vdenoise renders through rt_render_adaptive_vdenoised: the
  * adaptive frame filtered with each pixel's own sample count.
+ * -queue (with -vdenoise or -adaptive) turns rt_set_accumulate_queue on: their
+ * batches take the task-queue kernel; the frame is the same.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -38,7 +41,7 @@ int main(int argc, char** argv)
     int vdenoise = 0;
     rt_vdenoise_params vdn;
     rt_vdenoise_params_init(&vdn);
-    int adaptive = 0;
+    int adaptive = 0, queue = 0;
     rt_adaptive_params adp;
     rt_adaptive_params_init(&adp);
     double AO = 2.5, mx = 0, my = 0, mz = 0;
@@ -61,6 +64,8 @@ int main(int argc, char** argv)
         } else if (!strcmp(argv[i], "-adaptive") && i + 1 < argc) {
             adaptive = 1;
             adp.tolerance = (float)atof(argv[++i]);
+        } else if (!strcmp(argv[i], "-queue")) {
+            queue = 1;
         } else if (!strcmp(argv[i], "-move") && i + 3 < argc) {
             mx = atof(argv[++i]);
             my = atof(argv[++i]);
@@ -68,7 +73,8 @@ int main(int argc, char** argv)
         } else {
             fprintf(stderr, "usage: %s [-w W] [-s spp] [-b bounces] [-ao I] [-o out.ppm] "
                             "[-obj f.obj -mtl f.mtl [-move x y z]] [-devices N] [-denoise [iterations]] "
-                            "[-vdenoise [iterations]] [-adaptive TOL]\n"
+                            "[-vdenoise [iterations]] [-adaptive TOL] [-queue]\n"
+                            "  -queue: -vdenoise and -adaptive sample on the task-queue kernel (same frame)\n"
                             "  -adaptive with -vdenoise: the adaptive frame, filtered with each pixel's own sample count\n",
                     argv[0]);
             return 2;
@@ -134,6 +140,7 @@ int main(int argc, char** argv)
         if (rt_set_denoise_params(&dn)) { fprintf(stderr, "-denoise: %s\n", rt_last_error()); return 1; }
         rt_set_denoise_hook(rt_denoise_atrous);
     }
+    if (queue && (vdenoise || adaptive)) rt_set_accumulate_queue(1);
     size_t n = (size_t)W * H;
     rt_color* canva = (rt_color*)calloc(n, sizeof(rt_color));
     rt_color* albedo = (rt_color*)calloc(n, sizeof(rt_color));

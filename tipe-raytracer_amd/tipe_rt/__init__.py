@@ -126,6 +126,10 @@ def lib():
                                                      P(VDenoiseParams), C.c_void_p, C.c_size_t, P(Frame), C.c_void_p]
             L.rt_render_adaptive_vdenoised.argtypes = [P(Scene), P(Params), P(AdaptiveParams), P(VDenoiseParams),
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_set_accumulate_queue"):        # (added to ABI 5 as well)
+            L.rt_set_accumulate_queue.argtypes = [C.c_int]
+            L.rt_set_accumulate_queue.restype = C.c_int
+            L.rt_last_list_kernel.restype = C.c_char_p
         _lib = L
     return _lib
 
@@ -143,7 +147,7 @@ EXPORTED_SYMBOLS = ["rt_params_init", "rt_init", "rt_shutdown", "rt_last_error",
                     "rt_render_vdenoised", "rt_accumulate_list_async", "rt_adaptive_select_async",
                     "rt_adaptive_workspace_bytes", "rt_adaptive_params_init", "rt_adaptive_async",
                     "rt_resolve_adaptive_async", "rt_render_adaptive", "rt_vdenoise_adaptive_async",
-                    "rt_render_adaptive_vdenoised"]
+                    "rt_render_adaptive_vdenoised", "rt_set_accumulate_queue", "rt_last_list_kernel"]
 
 # rt_denoise_fn (rt.h): denoiser()'s signature, denoiser.h:31
 DENOISE_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p, Camera, C.c_void_p, C.c_void_p)
@@ -155,6 +159,19 @@ def set_zero_throughput_exit(enable):
     0 where that is exact (default on; frames are identical either way, only
     the counted work differs).  Returns the previous setting."""
     return bool(lib().rt_set_zero_throughput_exit(1 if enable else 0))
+
+
+def set_accumulate_queue(enable):
+    """rt_set_accumulate_queue (rt.h): launches with running sums
+    (accumulate_async, accumulate_list_async and what is built on them) take
+    the task-queue kernel where a render launch would (default off; the sums
+    are bit-identical either way).  Returns the previous setting."""
+    return bool(lib().rt_set_accumulate_queue(1 if enable else 0))
+
+
+def last_list_kernel():
+    """rt_last_list_kernel: the render kernel this thread's last list launch used."""
+    return lib().rt_last_list_kernel().decode()
 
 
 class reference_counts:

@@ -3,6 +3,7 @@
 
     tools/adaptive_bench.py [--scenes box,nature] [--size 1200x900] [--reps 5] [--warmup 1] [--label TAG]
                             [--first-half 8] [--max-rounds 5] [--tolerance 0.015625] [--no-rounds]
+                            [--queue off|on|both] [--ceiling SPP]
 
 Per scene, JSON lines (device-event times, every repetition listed so the spread shows):
   adaptive        rt_adaptive_async at the given parameters (A, B, d_rounds and the frame planes), its total
@@ -18,6 +19,12 @@ Per scene, JSON lines (device-event times, every repetition listed so the spread
                   dense fixed-grid kernel's on the same batch size over the whole frame (rt_accumulate_async:
                   the parent's code, the yardstick); round 0 also times the list kernel on a list of every
                   pixel, which separates the cost of the entry map from that of the pixels a list keeps.
+--queue: rt_set_accumulate_queue's setting for every timed call (default off; a library without the switch
+runs off only).  With "both" each repetition of a case runs once off and once on, alternating, and the case
+prints one line per setting ("queue": 0 / 1), so the two share the device's state.  What the accumulators hold
+is the same either way.
+--ceiling SPP adds two lines per scene: ceiling_accumulate, SPP samples as two rt_accumulate_async halves, and
+ceiling_render, rt_render_async at SPP (always the task-queue kernel: what an accumulate launch can reach).
 The box is the README scene (spheres only), nature the reference's RTX_MAP/nature mesh under its own camera."""
 import argparse
 import json
@@ -41,6 +48,8 @@ def main():
     ap.add_argument("--max-rounds", type=int, default=None)
     ap.add_argument("--tolerance", type=float, default=None)
     ap.add_argument("--no-rounds", action="store_true", help="skip the round-by-round lines")
+    ap.add_argument("--queue", choices=["off", "on", "both"], default="off")
+    ap.add_argument("--ceiling", type=int, default=0, help="SPP of the ceiling_accumulate / ceiling_render lines")
     args = ap.parse_args()
     import torch
     import tipe_rt
@@ -54,25 +63,46 @@ def main():
     adp = tipe_rt.adaptive_params(first_half=args.first_half, max_rounds=args.max_rounds, tolerance=args.tolerance)
     fh, R = adp.first_half, adp.max_rounds
     band = tipe_rt.band_tiling(0, H - 1)
+    has_switch = hasattr(tipe_rt.lib(), "rt_set_accumulate_queue")
+    if args.queue != "off" and not has_switch:
+        sys.exit("adaptive_bench: this library has no rt_set_accumulate_queue")
+    settings = {"off": [0], "on": [1], "both": [0, 1]}[args.queue]
+
+    def set_queue(q):
+        if has_switch:
+            tipe_rt.set_accumulate_queue(bool(q))
 
     def timed(call, reps=args.reps, warmup=args.warmup):
-        """Milliseconds of each repetition."""
+        """{setting: milliseconds of each repetition}; the settings alternate within a repetition."""
         for _ in range(warmup):
-            call()
+            for q in settings:
+                set_queue(q)
+                call()
         torch.cuda.synchronize()
-        out = []
+        out = {q: [] for q in settings}
         for _ in range(reps):
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            call()
-            t1.record()
-            torch.cuda.synchronize()
-            out.append(round(t0.elapsed_time(t1), 3))
+            for q in settings:
+                set_queue(q)
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                call()
+                t1.record()
+                torch.cuda.synchronize()
+                out[q].append(round(t0.elapsed_time(t1), 3))
+        set_queue(0)
         return out
 
     def emit(**kw):
         print(json.dumps(dict(label=args.label, W=W, H=H, first_half=fh, max_rounds=R,
                               tolerance=float(adp.tolerance), **kw)), flush=True)
+
+    def emit_each(ms, **kw):
+        """One line per setting of a timed() result."""
+        for q in settings:
+            emit(queue=q, ms=ms[q], **kw)
+
+    def rate(n, ms):
+        return round(n / (float(np.median(ms)) * 1e-3) / 1e6, 1) if n else None
 
     for name in args.scenes.split(","):
         if name == "nature":
@@ -104,8 +134,8 @@ def main():
         k = rounds.cpu().numpy()
         counts = 2.0 * fh * 2.0 ** (k - 1)
         mean = float(counts.mean())
-        emit(scene=name, what="adaptive", ms=ms, total_samples=float(counts.sum()), mean_spp=round(mean, 3),
-             share_per_round=[round(float((k == r).mean()), 4) for r in range(1, R + 1)])
+        emit_each(ms, scene=name, what="adaptive", bounces=bounces, total_samples=float(counts.sum()),
+                  mean_spp=round(mean, 3), share_per_round=[round(float((k == r).mean()), 4) for r in range(1, R + 1)])
 
         def uniform(half):
             def call():
@@ -138,14 +168,31 @@ def main():
             tipe_rt.vdenoise_async(W, H, acc[0].data_ptr(), acc[1].data_ptr(), half_mean, vdp, vws.data_ptr(), vbytes,
                                    planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(), stream=st)
 
-        emit(scene=name, what="adaptive_vdenoised", ms=timed(adaptive_vdenoised), mean_spp=round(mean, 3),
-             iterations=vdp.iterations)
-        emit(scene=name, what="uniform_vdenoised", spp=2 * half_mean, ms=timed(uniform_vdenoised),
-             iterations=vdp.iterations)
-        emit(scene=name, what="uniform_max", spp=2 * half_max, ms=timed(uniform(half_max)),
-             total_samples=2.0 * half_max * npx)
-        emit(scene=name, what="uniform_mean", spp=2 * half_mean, ms=timed(uniform(half_mean)),
-             total_samples=2.0 * half_mean * npx)
+        emit_each(timed(adaptive_vdenoised), scene=name, what="adaptive_vdenoised", mean_spp=round(mean, 3),
+                  iterations=vdp.iterations)
+        emit_each(timed(uniform_vdenoised), scene=name, what="uniform_vdenoised", spp=2 * half_mean,
+                  iterations=vdp.iterations)
+        emit_each(timed(uniform(half_max)), scene=name, what="uniform_max", spp=2 * half_max,
+                  total_samples=2.0 * half_max * npx)
+        emit_each(timed(uniform(half_mean)), scene=name, what="uniform_mean", spp=2 * half_mean,
+                  total_samples=2.0 * half_mean * npx)
+        if args.ceiling:
+            half_c = args.ceiling // 2
+
+            def ceiling_accumulate():
+                for j in range(2):
+                    tipe_rt.accumulate_async(ds, with_spp(half_c), j * half_c, band, acc[j].data_ptr(), st)
+
+            def ceiling_render():
+                tipe_rt.render_async(ds, with_spp(2 * half_c), band, planes[0].data_ptr(), planes[1].data_ptr(),
+                                     planes[2].data_ptr(), None, st)
+
+            for what, call in (("ceiling_accumulate", ceiling_accumulate), ("ceiling_render", ceiling_render)):
+                ms = timed(call)
+                for q in settings:
+                    emit(queue=q, ms=ms[q], scene=name, what=what, spp=2 * half_c, bounces=bounces,
+                         kernel=tipe_rt.last_render_kernel() if q == settings[-1] else None,
+                         msamples_per_s=rate(2.0 * half_c * npx, ms[q]))
 
         if args.no_rounds:
             ds.close()
@@ -165,8 +212,8 @@ def main():
                 tipe_rt.accumulate_async(ds, pb, o, band, scratch.data_ptr(), st)
 
             dense_ms = timed(dense)
-            line = dict(scene=name, what="round", round=r, batch=b, list_size=n_list, dense_ms=dense_ms,
-                        dense_msamples_per_s=round(npx * b / (float(np.median(dense_ms)) * 1e-3) / 1e6, 1))
+            lines = {q: dict(scene=name, what="round", queue=q, round=r, batch=b, list_size=n_list, dense_ms=dense_ms[q],
+                             dense_msamples_per_s=rate(npx * b, dense_ms[q])) for q in settings}
             if r == 0:
                 # the list kernel on every pixel against the dense kernel: what the entry map costs by itself
                 every = torch.arange(npx, dtype=torch.int32, device=dev)
@@ -177,8 +224,8 @@ def main():
                                                   scratch.data_ptr(), st)
 
                 full_ms = timed(full_list)
-                line.update(full_list_ms=full_ms, full_list_msamples_per_s=round(
-                    npx * b / (float(np.median(full_ms)) * 1e-3) / 1e6, 1))
+                for q in settings:
+                    lines[q].update(full_list_ms=full_ms[q], full_list_msamples_per_s=rate(npx * b, full_ms[q]))
                 for j in range(2):
                     tipe_rt.accumulate_async(ds, pb, o + j * b, band, acc[j].data_ptr(), st)
             else:
@@ -187,12 +234,13 @@ def main():
                                                   st)
 
                 list_ms = timed(listed)
-                line.update(list_ms=list_ms, list_msamples_per_s=round(
-                    n_list * b / (float(np.median(list_ms)) * 1e-3) / 1e6, 1) if n_list else None)
+                for q in settings:
+                    lines[q].update(list_ms=list_ms[q], list_msamples_per_s=rate(n_list * b, list_ms[q]))
                 for j in range(2):
                     tipe_rt.accumulate_list_async(ds, pb, o + j * b, lst.data_ptr(), cnt.data_ptr(), npx,
                                                   acc[j].data_ptr(), st)
-            emit(**line)
+            for q in settings:
+                emit(**lines[q])
             if r < R - 1:
                 tipe_rt.adaptive_select_async(W, H, acc[0].data_ptr(), acc[1].data_ptr(), n_r, float(adp.tolerance), r,
                                               lst.data_ptr(), cnt.data_ptr(), rounds.data_ptr(), ws.data_ptr(), nbytes,

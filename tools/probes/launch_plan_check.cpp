@@ -5,7 +5,8 @@
 // calls fill_kparams on the HostScene, then plan_render, and prints one JSON line
 // {"rc": 0, "plans": [...]} with one record per section.  Keys (all optional):
 // W H spp bounces chunks useAO AO compat semantics accel sky_mode ox oy oz (camera
-// origin) aperture_x aperture_y rows (local rows, default H) accumulate count.
+// origin) aperture_x aperture_y rows (local rows, default H) accumulate count
+// accumulate_queue (rt_set_accumulate_queue's switch, default 0).
 // In place of the scene sections,
 //   facts KEY VALUE ... end
 // gives the scalars the plan depends on with no scene: ns nt bvh_nodes bvh_depth
@@ -61,7 +62,7 @@ static void put_plan(const HostScene& hs)
     p.largeur_image = 40, p.hauteur_image = 30, p.nbRayonParPixel = 8, p.nbRebondMax = 6;
     p.spp_chunks = 4, p.compat_int_truncation = 1, p.AO_intensity = 2.5, p.focus_distance = 3.0;
     int rows = -1;
-    bool accumulate = false, count = false;
+    bool accumulate = false, count = false, accumulate_queue = false;
     std::string k;
     for (double v; pair(k, v);) {
         if (k == "W") p.largeur_image = (int)v;
@@ -83,6 +84,7 @@ static void put_plan(const HostScene& hs)
         else if (k == "rows") rows = (int)v;
         else if (k == "accumulate") accumulate = v != 0;
         else if (k == "count") count = v != 0;
+        else if (k == "accumulate_queue") accumulate_queue = v != 0;
         else std::fprintf(stderr, "launch_plan_check: unknown param %s\n", k.c_str()), std::exit(2);
     }
     const rt_tiling t = {0, rows < 0 ? p.hauteur_image : rows, 0, 1, 1};
@@ -91,6 +93,7 @@ static void put_plan(const HostScene& hs)
     fill_kparams(hs, hs.facts, &p, &t, true, kp, uni);
     double sums = 0.0;
     if (accumulate) kp.sums = &sums;                 // (rt_accumulate_async; never read here)
+    kp.acc_queue = accumulate_queue ? 1 : 0;
     const RenderPlan pl = plan_render(kp, count);
     std::printf("{\"name\": \"%s\", \"queue\": %d, \"qb\": %d, \"opq\": %d, \"sky\": %d, \"ao\": %d, "
                 "\"cuda\": %d, \"bvh\": %d, \"wide\": %d, \"stack_cap\": %d, \"task_ok\": %d, \"band_rows\": %d, "
