@@ -253,8 +253,8 @@ const char* rt_last_render_kernel(void);
  * rt_adaptive_async) used; list launches do not report through
  * rt_last_render_kernel.  "render_kernel_list", "render_kernel_list<BVH>" or
  * "render_kernel_list_w" (a wide tree) = the fixed-grid list kernels;
- * "render_kernel_ql<QB=...>" = the task-queue list kernel of the pair that
- * rt_last_render_kernel names as "render_kernel_q<QB=...>"
+ * "render_kernel_ql<QB=...>" = the list form of render_kernel_q, of the pair
+ * that rt_last_render_kernel names as "render_kernel_q<QB=...>"
  * (rt_set_accumulate_queue); "none" before the first.  The choice never
  * changes a result.  Diagnostics and tests. */
 const char* rt_last_list_kernel(void);
@@ -472,8 +472,8 @@ int rt_set_zero_throughput_exit(int enable);
  * kernels by default.  With this switch on they take the task-queue kernel
  * wherever a render launch of the same scene and parameters would: the same
  * (QB, OPQ) pair, stack and row bands for rt_accumulate_async
- * (rt_last_render_kernel names it), "render_kernel_ql" of that pair for a
- * list (rt_last_list_kernel).  A slice partial starts at +0.0 and takes its
+ * (rt_last_render_kernel names it), the list form of render_kernel_q of that
+ * pair for a list (rt_last_list_kernel names it "render_kernel_ql").  A slice partial starts at +0.0 and takes its
  * samples in order on either kernel, and the partials are added to the running
  * sums in slice order, so every sum is bit-identical either way.  These
  * launches keep the fixed grid with the switch on: one sample slice

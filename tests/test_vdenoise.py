@@ -281,7 +281,8 @@ def test_new_kernels_use_no_scratch():
     txt = out.stdout + out.stderr
     assert out.returncode == 0, txt[-2000:]
     seen = set()
-    for name in ("prepare_kernel", "lum_kernel", "pass_kernel", "pass_tiled_kernel", "finish_kernel"):
+    # (prepare and finish: the <double> instantiations, as the symbols spell them)
+    for name in ("prepare_kernelIJdE", "lum_kernel", "pass_kernel", "pass_tiled_kernel", "finish_kernelIJdE"):
         m = re.search(r"Function Name: \S*vdenoise_" + name + r"E.*?ScratchSize \[bytes/lane\]: (\d+).*?"
                       r"SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", txt, re.S)
         assert m, (name, txt[-2000:])

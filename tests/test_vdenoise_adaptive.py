@@ -153,7 +153,8 @@ def test_new_kernels_use_no_scratch_and_keep_their_twins_occupancy():
         assert m, (name, txt[-2000:])
         return dict(zip(("vgprs", "scratch", "occupancy", "sgpr_spill", "spill"), map(int, m.groups())))
 
-    for new, twin in (("prepare_px_kernel", "prepare_kernel"), ("finish_px_kernel", "finish_kernel")):
+    # the <const int* __restrict__, int> instantiations against the <double> ones, as the symbols spell them
+    for new, twin in (("prepare_kernelIJrPKiiE", "prepare_kernelIJdE"), ("finish_kernelIJrPKiiE", "finish_kernelIJdE")):
         a, b = usage(new), usage(twin)
         print(new, a, "twin", b)
         assert (a["scratch"], a["spill"], a["sgpr_spill"]) == (0, 0, 0), (new, a)

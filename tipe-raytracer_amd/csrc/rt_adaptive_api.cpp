@@ -97,8 +97,8 @@ AdaptiveSelect select_args(int W, int H, void* workspace)
 // rt_last_list_kernel: the render kernel of the calling thread's last list launch.
 thread_local const char* t_last_list = "none";
 
-// render_kernel_ql's name for the plan's pair: the pair's render_kernel_q name
-// (rt_queue_variants.h) with the kernel's own name in front.
+// The reported name of render_kernel_q's list form for the plan's pair: the pair's
+// render_kernel_q name (rt_queue_variants.h) with "render_kernel_ql" in front.
 const char* list_queue_name(const RenderPlan& plan)
 {
     static const std::vector<std::string> names = [] {
@@ -122,7 +122,7 @@ int launch_list_on_stream(KParams& kp, const double* uni, const unsigned* d_list
     const int rc = keep_pool_memory();
     if (rc) return rc;
     // tree, width and sky -- and, with rt_set_accumulate_queue on, whether a render launch of kp takes the
-    // queue and with which pair: the list then takes render_kernel_ql of that pair (chunks > 1: task_ok)
+    // queue and with which pair: the list then takes the queue kernel's list form of that pair (chunks > 1: task_ok)
     const RenderPlan plan = plan_render(kp, false);
     const ListPlan bands = plan_list(kp.chunks, list_cap);
     const unsigned band = bands.band;

@@ -226,8 +226,8 @@ struct ListArgs {
     unsigned stride;         // entries of one chunk's plane of partial (the band size)
 };
 int launch_render_list(const KParams& kp, const RenderPlan& plan, const ListArgs& la, void* stream);
-// launcher (rt_queue_list.hip): the same band on the task-queue kernel render_kernel_ql<plan.qb, plan.opq, ...>
-// (plan.queue; chunks > 1), then combine_list_kernel.  kp.task_ctr: the launch's task counter, with
+// launcher (rt_queue_list.hip): the same band on the list form of render_kernel_q<plan.qb, plan.opq, ...>
+// (reported as render_kernel_ql; plan.queue; chunks > 1), then combine_list_kernel.  kp.task_ctr: the launch's task counter, with
 // kListTaskWords launch-private words kListTaskOffset words behind it (the band's task count, entry count and
 // division magic, which a prologue kernel derives from the device's count word).
 constexpr int kListTaskOffset = 16, kListTaskWords = 3;

@@ -281,12 +281,6 @@ static void launch_variant(const KParams& kp, const RenderPlan& pl, void* stream
     hipLaunchKernelGGL(kernel, grid_for(kp), dim3(256), 0, (hipStream_t)stream, kp);
 }
 
-// render_kernel_q's instantiations are picked by rt_queue_launch.h's table walk
-// (with_queue_variant), which hands the plan's QVariant to queue_kernel.
-using QueueKernel = void (*)(const KParams);
-template <class V>
-constexpr QueueKernel queue_kernel(V) { return render_kernel_q<V::SKY, V::AOM, V::QB, V::OPQ>; }
-
 static thread_local const char* t_last_kernel = "none";
 const char* last_render_kernel() { return t_last_kernel; }
 
@@ -296,10 +290,12 @@ int launch_render(const KParams& kp, const RenderPlan& pl, void* stream)
     t_last_kernel = pl.name;
     if (pl.queue) {
         const hipStream_t st = (hipStream_t)stream;
-        QueueKernel kernel = nullptr;
+        // the dense form of render_kernel_q, its instantiation picked by
+        // rt_queue_launch.h's table walk (with_queue_variant hands over the plan's QVariant)
+        QueueKernel<> kernel = nullptr;
         unsigned nb = 0;
         const bool listed = with_queue_variant(pl, [&](auto v) {
-            kernel = queue_kernel(v);
+            kernel = queue_kernel<>(v);
             nb = queue_grid(v, kernel, "render_kernel_q");
         });
         if (!listed) return (int)hipErrorInvalidValue;       // a (qb, opq) that plan_render cannot give

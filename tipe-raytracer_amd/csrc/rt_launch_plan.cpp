@@ -137,7 +137,7 @@ void set_tiling(KParams& kp, const rt_tiling* t, int H)
 //    combine_kernel adds the slice partials to the sums in slice order.  One
 //    slice (chunks 1) never has a task counter: it carries the sums through the
 //    samples on the fixed grid.  A list launch (rt_accumulate_list_async) takes
-//    render_kernel_ql of the same pair when this plan says queue.
+//    the list form of render_kernel_q of the same pair when this plan says queue.
 //  * Which queue kernel: one of rt_queue_variants.h's kQueueVariants, which says
 //    what each (QB, OPQ) pair walks, its stack and whether it has the far-origin
 //    margins.  The rules here admit a scene to a pair.

@@ -1,6 +1,9 @@
 // rt_queue.h -- The task-queue integrator QPath and its kernel render_kernel_q.
-// Part of the single translation unit rt_kernels.hip (included there, in this order).
+// Included, behind the headers of its helpers (rt_vec.h ... rt_fixed_grid.h, in
+// that order), by the two files that instantiate the kernel: rt_kernels.hip (the
+// dense form) and rt_queue_list.hip (the list form).
 #pragma once
+#include <type_traits>
 
 namespace rt {
 
@@ -453,16 +456,73 @@ __device__ __forceinline__ void decode_task(KParamsK K, unsigned t, uint32_t e[k
     e[4] = (uint32_t)chunk_start(K->S, K->chunks, K->chunk_taper, K->chunk_den, K->qm_chunks, chunk + 1u);
 }
 
+// The list form's second by-value argument, behind KParams in the kernarg segment,
+// through an address the compiler cannot see through (rt_vec.h kp_here).
+typedef const __attribute__((address_space(4))) ListArgs* ListArgsK;
+__device__ __forceinline__ ListArgsK la_here()
+{
+    static_assert(sizeof(KParams) % alignof(ListArgs) == 0, "ListArgs follows KParams without padding");
+    const __attribute__((address_space(4))) char* p =
+        (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(KParams);
+    asm volatile("" : "+s"(p));
+    return (ListArgsK)p;
+}
+
+// A list band's task words: written by the prologue (rt_queue_list.hip
+// list_tasks_kernel) before the render kernel starts and by nothing afterwards,
+// so they are read as constants (scalar loads).
+enum : int { LT_TASKS = 0, LT_ENTRIES = 1, LT_MAGIC = 2 };
+static_assert(LT_MAGIC + 1 == kListTaskWords, "the prologue's words");
+
+// decode_task for the tasks of a list band: e[0] the partial index
+// (~0: past the last task), e[1] the listed pixel (~0: an index at or beyond
+// W * H, a task without work, as in list_body), e[2] its row, e[3], e[4] the
+// slice's first and end sample.  The lanes of a wave decode consecutive tasks,
+// so list[] is read in one coalesced load unless the batch crosses a slice.
+__device__ __forceinline__ void decode_list_task(KParamsK K, unsigned t, uint32_t e[kTaskWords])
+{
+    const ListArgsK A = la_here();
+    const __attribute__((address_space(4))) unsigned* w =
+        (const __attribute__((address_space(4))) unsigned*)(K->task_ctr + kListTaskOffset);
+    // (every word is assigned once, by selects: an entry filled behind early
+    // returns kept a dead 20-byte stack object, and with it a scratch
+    // allocation, in the sphere-only instantiations)
+    const bool task = t < w[LT_TASKS];
+    unsigned r;
+    const unsigned q = udiv_q(t, w[LT_ENTRIES], w[LT_MAGIC], r);
+    const unsigned chunk = task ? q : 0u;
+    unsigned pixel = 0xffffffffu;                        // never a pixel: W * H <= 2^32 - 1 (validate_params)
+    if (task) pixel = A->list[A->e0 + r];
+    const bool work = pixel < (unsigned)K->W * (unsigned)K->H;
+    unsigned xr;
+    const unsigned row = udiv_q(pixel, (unsigned)K->W, K->qm_w, xr);
+    e[0] = task ? chunk * A->stride + r : 0xffffffffu;
+    e[1] = work ? pixel : 0xffffffffu;
+    e[2] = work ? row : 0xffffffffu;
+    e[3] = (uint32_t)chunk_start(K->S, K->chunks, K->chunk_taper, K->chunk_den, K->qm_chunks, chunk);
+    e[4] = (uint32_t)chunk_start(K->S, K->chunks, K->chunk_taper, K->chunk_den, K->qm_chunks, chunk + 1u);
+}
+
 // The (QB, OPQ) pairs are rt_queue_variants.h's, the constants QVariant's (V).
 // QB_WIDE: a wide tree (rt_bvh.h BvhBuild::wide) -- the non-opaque deep-tree
 // kernel (QB_DEEP, not OPQ: every material branch, the adaptive visit count, the
 // far-origin margins, the walk priority) over the BvhNodeW nodes kp.bvhw with
 // the 24-bit stack bvh_stack_qw; its 46 KiB of LDS allow three blocks per CU,
 // RT_WAVES_PER_SIMD_QW waves per SIMD.
-template <bool SKY, int AOM, int QB, bool OPQ = false>
+// TAIL: the kernel's arguments behind KParams, and with them its form.  None: the
+// dense form, whose tasks are a band's (chunk, pixel) pairs (decode_task).
+// ListArgs: the list form over a compacted list of pixels (rt_queue_list.hip),
+// whose tasks decode_list_task reads through la_here(); kp.partial is then the
+// band's partials.  Step 3's two decoder calls are all that depends on the pack.
+// The round loop stays in this one __global__ function: moved into a __device__
+// function that two kernels call, it is allocated other registers in 12 to 28 of
+// the dense instantiations (tools/isa_same.py pins their machine code).
+template <bool SKY, int AOM, int QB, bool OPQ = false, class... TAIL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QVariant<SKY, AOM, QB, OPQ>::WAVES)))
-void render_kernel_q(const KParams kp)
+void render_kernel_q(const KParams kp, const TAIL...)
 {
+    constexpr bool LIST = sizeof...(TAIL) == 1 && (std::is_same_v<TAIL, ListArgs> && ...);
+    static_assert(LIST || sizeof...(TAIL) == 0, "the tail is empty (dense) or ListArgs (list)");
     using V = QVariant<SKY, AOM, QB, OPQ>;
     constexpr bool PD = V::PD, TTAB = V::TTAB;
     constexpr int NTOP = V::NTOP, HN = V::HN;
@@ -621,7 +681,8 @@ void render_kernel_q(const KParams kp)
                 nb = __shfl(nb, __ffsll((long long)nm) - 1, 64);
                 if constexpr (TTAB) {
                     uint32_t d[kTaskWords];
-                    decode_task(K, nb + (unsigned)lane, d);
+                    if constexpr (LIST) decode_list_task(K, nb + (unsigned)lane, d);
+                    else decode_task(K, nb + (unsigned)lane, d);
 #pragma unroll
                     for (int j = 0; j < kTaskWords; ++j) tw[j * 64 + lane] = d[j];
                     if (need && !old) {
@@ -637,9 +698,12 @@ void render_kernel_q(const KParams kp)
                 qb += nn;
             }
             if (need) {
-                if constexpr (!TTAB) decode_task(K, t, e);
+                if constexpr (!TTAB) {
+                    if constexpr (LIST) decode_list_task(K, t, e);
+                    else decode_task(K, t, e);
+                }
                 ++ntasks;
-                if (owns) {              // task done: its sums to the chunk partials
+                if (owns) {              // task done: its sums to the chunk partials (list form: the band's)
                     double* q = K->partial + (size_t)qidx * 9;
 #pragma unroll
                     for (int j = 0; j < 9; ++j) q[j] = acc[j * 256];
@@ -647,7 +711,7 @@ void render_kernel_q(const KParams kp)
                 }
                 if (e[0] == 0xffffffffu) {
                     L.state = SM_DONE;
-                } else if (e[1] != 0xffffffffu) {  // else a padding row: the lane takes its next task next round
+                } else if (e[1] != 0xffffffffu) {  // else no work (a padding row; list: not a pixel): the next task next round
                     qidx = e[0];
                     if constexpr (PD) {
                         const PhiloxHead h = philox_head(e[1], K->key0);

@@ -1,6 +1,6 @@
 // rt_queue_launch.h — host side of a task-queue launch, shared by the two files
-// that instantiate queue kernels: rt_kernels.hip (render_kernel_q) and
-// rt_queue_list.hip (render_kernel_ql).  Included after rt_queue.h.
+// that instantiate render_kernel_q: rt_kernels.hip (the dense form) and
+// rt_queue_list.hip (the list form).  Included after rt_queue.h.
 #pragma once
 #include <atomic>
 #include <cstdio>
@@ -36,6 +36,13 @@ static bool with_queue_variant(const RenderPlan& pl, F&& f)
         return false;
     }
 }
+
+// Variant V's render_kernel_q with the arguments TAIL behind KParams: none (the
+// dense form) or ListArgs (the list form).
+template <class... TAIL>
+using QueueKernel = void (*)(const KParams, const TAIL...);
+template <class... TAIL, class V>
+constexpr QueueKernel<TAIL...> queue_kernel(V) { return render_kernel_q<V::SKY, V::AOM, V::QB, V::OPQ, TAIL...>; }
 
 // Resident blocks of variant V's queue kernel `kernel` on this device: the grid
 // of its launches.  Cached per device, variant and kernel type (one table per

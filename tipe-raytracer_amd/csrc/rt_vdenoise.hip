@@ -21,32 +21,6 @@ namespace {
 // Grid-stride kernels: 2048 blocks of 256 threads fill the 256 CUs (8 blocks each).
 unsigned grid_1d(long long n) { return (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048); }
 
-// the two accumulators -> the planes c, v, a, nn
-__global__ __launch_bounds__(256) void vdenoise_prepare_kernel(long long npx, const double* __restrict__ sums_a,
-                                                               const double* __restrict__ sums_b, double rap,
-                                                               float* __restrict__ c3, float* __restrict__ v1,
-                                                               float* __restrict__ a3, float* __restrict__ n3)
-{
-    for (long long px = (long long)blockIdx.x * blockDim.x + threadIdx.x; px < npx;
-         px += (long long)gridDim.x * blockDim.x) {
-        const double* sa = sums_a + px * 9;
-        const double* sb = sums_b + px * 9;
-        float ma[9], mb[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            ma[k] = (float)(rap * sa[k]);
-            mb[k] = (float)(rap * sb[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            c3[px * 3 + k] = 0.5f * (ma[k] + mb[k]);
-            a3[px * 3 + k] = 0.5f * (ma[3 + k] + mb[3 + k]);
-            n3[px * 3 + k] = 0.5f * (ma[6 + k] + mb[6 + k]);
-        }
-        v1[px] = lum2(0.5f * (ma[0] - mb[0]), 0.5f * (ma[1] - mb[1]), 0.5f * (ma[2] - mb[2]));
-    }
-}
-
 // n_p of rt.h "per-pixel sample counts": first_half * 2^(k-1) samples per
 // accumulator, k = rounds[px] under adaptive_resolve_kernel's clamp (rt_adaptive.hip)
 __device__ __forceinline__ double pixel_count(const int* __restrict__ rounds, long long px, int first_half)
@@ -55,18 +29,34 @@ __device__ __forceinline__ double pixel_count(const int* __restrict__ rounds, lo
     return (double)((long long)first_half << (k - 1));
 }
 
-// vdenoise_prepare_kernel with rap = 1.0 / n_p per pixel: one more 4-byte load
-// and one double division.  A kernel of its own with the twin's text: a device
-// function shared by both moves the twin's machine code (54 VGPRs for 53).
-__global__ __launch_bounds__(256) void vdenoise_prepare_px_kernel(long long npx, const double* __restrict__ sums_a,
-                                                                  const double* __restrict__ sums_b,
-                                                                  const int* __restrict__ rounds, int first_half,
-                                                                  float* __restrict__ c3, float* __restrict__ v1,
-                                                                  float* __restrict__ a3, float* __restrict__ n3)
+// What pixel px's sums are scaled by, from the count arguments N... of the prepare
+// and finish kernels.  <double>: every pixel holds n samples per accumulator and
+// the host passes the reciprocal, 1.0 / n (prepare) or 1.0 / (2 n) (finish).
+// <const int* __restrict__, int>: rounds and first_half, n_p per pixel -- one more
+// 4-byte load and one double division.  (The arguments stay a pack and the loops
+// stay in the kernels: a struct of the two costs the per-pixel forms two
+// instructions, a device function around the loop the uniform forms a VGPR.)
+__device__ __forceinline__ double mean_scale(long long, double rap) { return rap; }
+__device__ __forceinline__ double mean_scale(long long px, const int* __restrict__ rounds, int first_half)
+{
+    return 1.0 / pixel_count(rounds, px, first_half);
+}
+__device__ __forceinline__ double sum_scale(long long, double rap2) { return rap2; }
+__device__ __forceinline__ double sum_scale(long long px, const int* __restrict__ rounds, int first_half)
+{
+    return 1.0 / (2.0 * pixel_count(rounds, px, first_half));
+}
+
+// the two accumulators -> the planes c, v, a, nn
+template <class... N>
+__global__ __launch_bounds__(256) void vdenoise_prepare_kernel(long long npx, const double* __restrict__ sums_a,
+                                                               const double* __restrict__ sums_b, const N... n,
+                                                               float* __restrict__ c3, float* __restrict__ v1,
+                                                               float* __restrict__ a3, float* __restrict__ n3)
 {
     for (long long px = (long long)blockIdx.x * blockDim.x + threadIdx.x; px < npx;
          px += (long long)gridDim.x * blockDim.x) {
-        const double rap = 1.0 / pixel_count(rounds, px, first_half);
+        const double rap = mean_scale(px, n...);
         const double* sa = sums_a + px * 9;
         const double* sb = sums_b + px * 9;
         float ma[9], mb[9];
@@ -243,41 +233,17 @@ __device__ __forceinline__ int cvt_i32_x86(double x)
 
 // filtered colour -> canva = write_color_canva((double)c, 1) (rtutility.h:56-71,
 // as write_pixel), radiance = (double)c; albedo / normal = (A + B) * rap2
+template <class... N>
 __global__ __launch_bounds__(256) void vdenoise_finish_kernel(long long npx, const float* __restrict__ c3,
                                                               const double* __restrict__ sums_a,
-                                                              const double* __restrict__ sums_b, double rap2,
+                                                              const double* __restrict__ sums_b, const N... n,
                                                               double* __restrict__ canva, double* __restrict__ albedo,
                                                               double* __restrict__ normal,
                                                               double* __restrict__ radiance)
 {
     for (long long px = (long long)blockIdx.x * blockDim.x + threadIdx.x; px < npx;
          px += (long long)gridDim.x * blockDim.x) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float c = c3[px * 3 + k];
-            double r = (double)sqrtf(c);
-            r = r < 0.0 ? 0.0 : (r > 0.999 ? 0.999 : r);
-            canva[px * 3 + k] = (double)cvt_i32_x86(256 * r);
-            if (radiance) radiance[px * 3 + k] = (double)c;
-            if (albedo) albedo[px * 3 + k] = (sums_a[px * 9 + 3 + k] + sums_b[px * 9 + 3 + k]) * rap2;
-            if (normal) normal[px * 3 + k] = (sums_a[px * 9 + 6 + k] + sums_b[px * 9 + 6 + k]) * rap2;
-        }
-    }
-}
-
-// vdenoise_finish_kernel with rap2 = 1.0 / (2 n_p) per pixel (its own kernel, as the prepare twin)
-__global__ __launch_bounds__(256) void vdenoise_finish_px_kernel(long long npx, const float* __restrict__ c3,
-                                                                 const double* __restrict__ sums_a,
-                                                                 const double* __restrict__ sums_b,
-                                                                 const int* __restrict__ rounds, int first_half,
-                                                                 double* __restrict__ canva,
-                                                                 double* __restrict__ albedo,
-                                                                 double* __restrict__ normal,
-                                                                 double* __restrict__ radiance)
-{
-    for (long long px = (long long)blockIdx.x * blockDim.x + threadIdx.x; px < npx;
-         px += (long long)gridDim.x * blockDim.x) {
-        const double rap2 = 1.0 / (2.0 * pixel_count(rounds, px, first_half));
+        const double rap2 = sum_scale(px, n...);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float c = c3[px * 3 + k];
@@ -295,8 +261,8 @@ __global__ __launch_bounds__(256) void vdenoise_finish_px_kernel(long long npx, 
 
 size_t vdenoise_scalar_floats(long long npx) { return ((size_t)npx + 63) / 64 * 64; }
 
-// rounds null: spp_half samples per accumulator in every pixel; else the _px forms of prepare and finish
-// with first_half = spp_half.  Between the two the filter does not know the counts.
+// rounds null: spp_half samples per accumulator in every pixel; else the per-pixel forms of prepare and
+// finish with first_half = spp_half.  Between the two the filter does not know the counts.
 int launch_vdenoise(int W, int H, const double* sums_a, const double* sums_b, const int* rounds, int spp_half,
                     int iterations, float sigma_luminance, float sigma_normal, float sigma_albedo, float* workspace,
                     double* canva, double* albedo, double* normal, double* radiance, void* stream)
@@ -311,10 +277,10 @@ int launch_vdenoise(int W, int H, const double* sums_a, const double* sums_b, co
     float* L = workspace + 4 * plane3 + 2 * plane1;
     const double n = (double)spp_half;
     if (rounds)
-        hipLaunchKernelGGL(vdenoise_prepare_px_kernel, dim3(grid_1d(npx)), dim3(256), 0, st, npx, sums_a, sums_b,
-                           rounds, spp_half, c[0], v[0], a3, n3);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(vdenoise_prepare_kernel<const int* __restrict__, int>), dim3(grid_1d(npx)),
+                           dim3(256), 0, st, npx, sums_a, sums_b, rounds, spp_half, c[0], v[0], a3, n3);
     else
-        hipLaunchKernelGGL(vdenoise_prepare_kernel, dim3(grid_1d(npx)), dim3(256), 0, st, npx, sums_a, sums_b,
+        hipLaunchKernelGGL(vdenoise_prepare_kernel<double>, dim3(grid_1d(npx)), dim3(256), 0, st, npx, sums_a, sums_b,
                            1.0 / n, c[0], v[0], a3, n3);
     const float sl2 = sigma_luminance * sigma_luminance, sn2 = sigma_normal * sigma_normal,
                 sa2 = sigma_albedo * sigma_albedo;
@@ -335,10 +301,10 @@ int launch_vdenoise(int W, int H, const double* sums_a, const double* sums_b, co
         }
     }
     if (rounds)
-        hipLaunchKernelGGL(vdenoise_finish_px_kernel, dim3(grid_1d(npx)), dim3(256), 0, st, npx, c[iterations & 1],
-                           sums_a, sums_b, rounds, spp_half, canva, albedo, normal, radiance);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(vdenoise_finish_kernel<const int* __restrict__, int>), dim3(grid_1d(npx)),
+                           dim3(256), 0, st, npx, c[iterations & 1], sums_a, sums_b, rounds, spp_half, canva, albedo, normal, radiance);
     else
-        hipLaunchKernelGGL(vdenoise_finish_kernel, dim3(grid_1d(npx)), dim3(256), 0, st, npx, c[iterations & 1],
+        hipLaunchKernelGGL(vdenoise_finish_kernel<double>, dim3(grid_1d(npx)), dim3(256), 0, st, npx, c[iterations & 1],
                            sums_a, sums_b, 1.0 / (2.0 * n), canva, albedo, normal, radiance);
     return (int)hipGetLastError();
 }

@@ -10,7 +10,8 @@ pass (ceil(W/64) * ceil(H/4) blocks).  A call of the variance-guided filter
 (--filter vdenoise: the vdenoise_* kernels) has the variance blur (lum) in
 front of each pass kernel; it is reported next to its pass.  --filter
 vdenoise_px takes the calls of rt_vdenoise_adaptive_async instead (prepare and
-finish are the _px kernels), --filter vdenoise those of rt_vdenoise_async.  The first --skip
+finish are the <const int*, int> instantiations of their kernels, the uniform
+forms <double>), --filter vdenoise those of rt_vdenoise_async.  The first --skip
 calls of each size are warm-up.  Prints, per size and pass, the median and
 minimum kernel time and the compulsory-traffic rate (48 B/pixel for the
 a-trous pass, 68 B/pixel for the variance-guided pass with its blur) / median
@@ -21,6 +22,8 @@ import json
 import statistics
 
 HBM_ACHIEVABLE = 6.3e12
+# vdenoise_prepare_kernel's per-pixel instantiation, as a trace names it demangled or mangled
+PREPARE_PX = ("prepare_kernel<int const", "prepare_kernel<const int", "prepare_kernelIJrPKi")
 
 
 def main():
@@ -45,7 +48,7 @@ def main():
         us = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
         short = ("prepare" if "prepare" in name else "finish" if "finish" in name else
                  "lum" if "_lum_" in name else "tiled" if "tiled" in name else "plain")
-        if short == "prepare" and ("prepare_px" in name) != px:
+        if short == "prepare" and any(p in name for p in PREPARE_PX) != px:
             cur = None                           # the other form's call
         elif short == "prepare":
             cur = {"prepare": us, "passes": [], "lum": [], "grid0": None, "t0": int(r["Start_Timestamp"])}

@@ -21,7 +21,7 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYM = sys.argv[1] if len(sys.argv) > 1 else "_ZN2rt15render_kernel_qILb0ELi0ELin2ELb0EEEvNS_7KParamsE"
+SYM = sys.argv[1] if len(sys.argv) > 1 else "_ZN2rt15render_kernel_qILb0ELi0ELin2ELb0EJEEEvNS_7KParamsEDpKT3_"
 ASM = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "tipe-raytracer_amd", "rt_kernels_g.s")
 CSRC = os.path.join(ROOT, "tipe-raytracer_amd", "csrc")
 SRC = {f: os.path.join(CSRC, f) for f in ("rt_kernels.hip", "rt_device_math.h", "rt_shared_math.h", "rt_vec.h", "rt_spheres.h",
