@@ -53,7 +53,10 @@ extern "C" {
  *    filters an adaptive result (rt_vdenoise_adaptive_async,
  *    rt_render_adaptive_vdenoised); the task-queue kernel for launches with
  *    running sums, behind a switch (rt_set_accumulate_queue,
- *    rt_last_list_kernel).
+ *    rt_last_list_kernel); the packed canva transport (rt_canva_pack_async,
+ *    rt_canva_unpack_async, rt_canva_unpack_host, rt_assemble_packed_async,
+ *    rt_set_fill_packed_canva, and the flag RT_GATHER_PACKED_CANVA of
+ *    rt_params.gather, which older libraries refuse with RT_EINVAL).
  * A caller compares rt_abi_version() with the RT_ABI_VERSION it was built
  * against before passing rt_params or counter arrays.                   */
 #define RT_ABI_VERSION 5
@@ -131,6 +134,15 @@ typedef struct rt_params {
  * the other; rt_last_gather_transport() names the one a call used. */
 #define RT_GATHER_RCCL 0
 #define RT_GATHER_PEER 1
+/* A flag, OR-ed to either transport (default: not set): the canva travels
+ * packed, 4 bytes a pixel instead of 24 ("packed canva transport" below).
+ * Each slot packs its canva behind its render; RCCL moves the words in an
+ * ncclGather of ncclUint32 in the same group as the ncclFloat64 gather of the
+ * other requested planes, PEER in a hipMemcpyPeerAsync per slot; the first
+ * device widens them while it un-permutes (rt_assemble_packed_async).  The
+ * frame is bit for bit the one without the flag; albedo, normal and radiance
+ * travel as before.  rt_last_gather_transport() then ends in ", canva 4 B/px". */
+#define RT_GATHER_PACKED_CANVA 0x100
 
 /* rt_params.semantics.  MAIN_C (default) is main.c, the authoritative CPU
  * path.  CUDA is main_cuda.cu's integrator, the reference's
@@ -359,7 +371,8 @@ int rt_render_gather_async(const rt_scene* scene, const rt_params* params, int t
                            void* hip_stream);
 /* The transport the calling thread's last rt_render_gather_async used:
  * "rccl: ncclGather, RCCL x.y.z (library path), N ranks" or "peer:
- * hipMemcpyPeerAsync, N slots"; "none" before the first. */
+ * hipMemcpyPeerAsync, N slots", each followed by ", canva 4 B/px" when the call
+ * had RT_GATHER_PACKED_CANVA; "none" before the first. */
 const char* rt_last_gather_transport(void);
 /* Peer access the gathers use from dst_device to src_device, enabled on
  * first use per pair: 1 = enabled (copy engines read over xGMI; also the
@@ -371,6 +384,44 @@ const char* rt_last_gather_transport(void);
  * xGMI copies) have only run in tests on machines with >= 2 GPUs; the
  * builder's own GPU box has one, where every slot is device 0. */
 int rt_peer_access(int dst_device, int src_device);
+
+/* ---- packed canva transport: 4 bytes a pixel where a frame leaves a device -- */
+/* A canva channel as write_color_canva (every render's canva, rt_resolve_async,
+ * the denoisers' finish) writes it is one of 257 values: an integer 0..255
+ * stored as a double, or -2147483648.0, which (int) of a NaN radiance gives.
+ * 257^3 > 2^24, so a packed pixel is one 32-bit word
+ *   f0 | f1 << 9 | f2 << 18
+ * where field f of a channel is its value for +0.0, 1.0, ..., 255.0 and 256
+ * (the marker) for everything else.  Unpacking gives (double)f for f < 256 and
+ * -2147483648.0 for every other field (256, and 257..511, which no pack
+ * writes).  Bits 27..31 are written as zero and ignored on unpack.
+ * ONLY the 257 values above round-trip exactly.  Any other channel value --
+ * NaN, a fraction, 256.0, -1.0, -0.0, an infinity -- packs as the marker and
+ * comes back as -2147483648.0: the format is for canvas, not for albedo,
+ * normal or radiance planes.
+ *
+ * rt_canva_pack_async / rt_canva_unpack_async: n pixels between device arrays
+ * on `hip_stream` (the current device); rt_canva_unpack_host: the same
+ * widening in plain C on host arrays, no device involved.
+ * rt_assemble_packed_async: rt_assemble_async on a rank-major gather of packed
+ * blocks (rank_stride in pixels; 0: rows_per_rank*W), widening as it
+ * un-permutes; same arguments and geometry rules otherwise.
+ * RT_EINVAL before any device work for a NULL pointer, n < 1 or n above 2^30,
+ * and a packed pointer that is not 4-byte aligned. */
+int rt_canva_pack_async(long long n, const rt_color* canva, unsigned* packed, void* hip_stream);
+int rt_canva_unpack_async(long long n, const unsigned* packed, rt_color* canva, void* hip_stream);
+int rt_canva_unpack_host(long long n, const unsigned* packed, rt_color* canva);
+int rt_assemble_packed_async(const unsigned* gathered, long long rank_stride, int world,
+                             int tile_rows, int rows_per_rank, int W, int H,
+                             rt_color* out, void* hip_stream);
+/* rt_render_rows / rt_fill_canva with this switch on: the rendered rows' canva
+ * is packed on the render's stream, copied to the host at 4 bytes a pixel and
+ * widened into the caller's rows by rt_canva_unpack_host; albedo and normal
+ * are copied as before.  The arrays the caller receives are bit for bit the
+ * same, only the named rows are written, and concurrent calls on disjoint
+ * rows stay safe.  Process-wide and atomic, default off; read once per call.
+ * Returns the previous setting. */
+int rt_set_fill_packed_canva(int enable);
 
 /* ---- instrumentation (roofline accounting, tests) ----------------------- */
 enum {

@@ -126,7 +126,8 @@ int validate_params(const rt_params* p)
         return fail(RT_EUNSUPPORTED, "RT_PREC_FP32 was removed (r05): its 1.1-3.4e-4 per-channel RMSE against the "
                                      "reference exceeded north_star's 1e-4; only the bit-exact FP64 path renders");
     if (p->precision != RT_PREC_FP64) return fail(RT_EINVAL, "unknown precision %d", p->precision);
-    if (p->gather != RT_GATHER_RCCL && p->gather != RT_GATHER_PEER)
+    const int transport = p->gather & ~RT_GATHER_PACKED_CANVA;        // the flag goes with either transport
+    if (transport != RT_GATHER_RCCL && transport != RT_GATHER_PEER)
         return fail(RT_EINVAL, "unknown gather transport %d", p->gather);
     if ((unsigned long long)p->largeur_image * (unsigned long long)p->hauteur_image > 0xffffffffull)
         return fail(RT_EUNSUPPORTED, "pixel index exceeds the 32-bit Philox counter word");

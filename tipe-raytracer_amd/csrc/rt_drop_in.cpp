@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "rt_host_slots.h"
+#include "rt_pack.h"
 
 using namespace rt;
 
@@ -153,7 +154,7 @@ int rt::scene_cache_get(int device, const rt_scene* sc, std::shared_ptr<rt_devic
 }
 
 int RenderSlot::render(int device, const rt_scene* scene, const rt_params* params, const rt_tiling& t, int row_end,
-                       rt_color* const* want, hipEvent_t go)
+                       rt_color* const* want, hipEvent_t go, bool pack_canva)
 {
     int rc;
     if ((rc = scene_cache_get(device, scene, sc)) || (rc = stream.acquire(device, !go))) return rc;
@@ -162,7 +163,7 @@ int RenderSlot::render(int device, const rt_scene* scene, const rt_params* param
     size_t n = 0;
     for (int pl = 0; pl < 4; ++pl) n += want[pl] ? plane : 0;
     hipError_t e = go ? hipStreamWaitEvent(stream->st, go, 0) : hipSuccess;
-    if (e == hipSuccess) e = buf.alloc(n * sizeof(double), stream->st, device);
+    if (e == hipSuccess) e = buf.alloc(n * sizeof(double) + (pack_canva ? plane / 3 * sizeof(unsigned) : 0), stream->st, device);
     if (e == hipSuccess && go) e = rendered.create();
     if (e != hipSuccess) return fail(RT_EDEVICE, "device %d frame: %s", device, hipGetErrorString(e));
     KParams kp;
@@ -177,6 +178,10 @@ int RenderSlot::render(int device, const rt_scene* scene, const rt_params* param
             next += plane;
         }
     if ((rc = launch_on_stream(kp, uni, stream->st, false))) return rc;
+    if (pack_canva) {
+        packed = (unsigned*)((double*)buf.p + n);
+        if ((rc = rt_canva_pack_async((long long)(plane / 3), (const rt_color*)kp.canva, packed, stream->st))) return rc;
+    }
     if (go && (e = hipEventRecord(rendered, stream->st)) != hipSuccess)
         return fail(RT_EDEVICE, "device %d event: %s", device, hipGetErrorString(e));
     return RT_OK;
@@ -236,6 +241,11 @@ int rt_render_rows(const rt_scene* scene, const rt_params* params, int row_hi, i
     const int ntiles = (nrows + k - 1) / k;
     rt_color* outs[4] = {canva, albedo, normal, nullptr};
     const int nplanes = 3;
+    // rt_set_fill_packed_canva: the canva leaves the device as one word per
+    // pixel (packed behind the render) and is widened into the caller's rows
+    const bool packed = fill_packed_canva();
+    if (packed && (long long)((nrows + ndev - 1) / ndev) * W > kPackMaxPixels)     // the busiest device's rows
+        return fail(RT_EINVAL, "packed canva: more than 2^30 pixels per device");
     // a slot's destructor frees its planes in stream order, then waits for its
     // stream and hands it back: on every return below
     std::vector<RenderSlot> slots((size_t)ndev);
@@ -243,7 +253,8 @@ int rt_render_rows(const rt_scene* scene, const rt_params* params, int row_hi, i
     // 1. every device: cached scene, pooled stream, stream-ordered planes, launch
     for (int q = 0; q < ndev; ++q) {
         const rt_tiling t{row_lo, k, q, ndev, tiles_of(q)};
-        if (t.n_tiles > 0 && (rc = slots[(size_t)q].render(devs[(size_t)q], scene, params, t, row_hi + 1, outs, nullptr)))
+        if (t.n_tiles > 0 &&
+            (rc = slots[(size_t)q].render(devs[(size_t)q], scene, params, t, row_hi + 1, outs, nullptr, packed)))
             return rc;
     }
     // 2. every device: D2H of the requested planes into its stream's pinned
@@ -257,8 +268,12 @@ int rt_render_rows(const rt_scene* scene, const rt_params* params, int row_hi, i
         size_t off = 0;
         for (int pl = 0; pl < nplanes && e == hipSuccess; ++pl) {
             if (!outs[pl]) continue;
-            e = hipMemcpyAsync((double*)s.stream->host + off, (const double*)s.buf.p + off, s.plane * sizeof(double),
-                               hipMemcpyDeviceToHost, s.stream->st);
+            if (pl == 0 && packed)         // the words sit behind the planes, on the device and in the staging
+                e = hipMemcpyAsync((char*)s.stream->host + ((char*)s.packed - (char*)s.buf.p), s.packed,
+                                   s.plane / 3 * sizeof(unsigned), hipMemcpyDeviceToHost, s.stream->st);
+            else
+                e = hipMemcpyAsync((double*)s.stream->host + off, (const double*)s.buf.p + off,
+                                   s.plane * sizeof(double), hipMemcpyDeviceToHost, s.stream->st);
             if (e == hipSuccess) e = hipEventRecord(s.stream->plane_done[pl], s.stream->st);
             off += s.plane;
         }
@@ -281,11 +296,17 @@ int rt_render_rows(const rt_scene* scene, const rt_params* params, int row_hi, i
                 return fail(RT_EDEVICE, "device %d render/copy: %s", devs[(size_t)q], hipGetErrorString(e));
             // this device's local rows [r0, r1), tile by tile (the part of each that lies in the range):
             // tile lt = caller rows row_lo + (q + lt * ndev) * k + [0, k); rows past row_hi are padding
-            auto rows = [&, src0, pl](int r0, int r1) {
+            const unsigned* words =
+                pl == 0 && packed ? (const unsigned*)((const char*)s.stream->host + ((char*)s.packed - (char*)s.buf.p))
+                                  : nullptr;
+            auto rows = [&, src0, pl, words](int r0, int r1) {
                 for (int r = r0; r < r1; r += k - r % k) {
                     const int gr = row_lo + (q + r / k * ndev) * k + r % k;
                     const int n = std::min({k - r % k, r1 - r, row_hi + 1 - gr});
-                    if (n > 0)
+                    if (n <= 0) continue;
+                    if (words)
+                        (void)rt_canva_unpack_host((long long)W * n, words + (size_t)r * W, outs[pl] + (size_t)gr * W);
+                    else
                         std::memcpy(outs[pl] + (size_t)gr * W, src0 + (size_t)r * W * 3, sizeof(double) * 3 * (size_t)W * n);
                 }
             };

@@ -8,12 +8,14 @@
 // transfers, which is all ncclGather, rccl.h:745, would issue for it inside one
 // process), then the assemble kernel un-permutes them into row order.
 #include <array>
+#include <cstdint>
 #include <cstdlib>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "rt_host_slots.h"
+#include "rt_pack.h"
 #include "rt_rccl.h"
 
 using namespace rt;
@@ -103,6 +105,21 @@ int rt_assemble_async(const rt_color* gathered, long long rank_stride, int world
     return RT_OK;
 }
 
+int rt_assemble_packed_async(const unsigned* gathered, long long rank_stride, int world, int tile_rows,
+                             int rows_per_rank, int W, int H, rt_color* out, void* hip_stream)
+{
+    int rc;
+    if (!gathered || !out) return fail(RT_EINVAL, "NULL buffer");
+    if ((uintptr_t)gathered % 4) return fail(RT_EINVAL, "packed canva is not 4-byte aligned");
+    if ((rc = check_gather_geometry(world, tile_rows, rows_per_rank, W, H))) return rc;
+    if (rank_stride == 0) rank_stride = (long long)rows_per_rank * W;
+    if (rank_stride < (long long)rows_per_rank * W) return fail(RT_EINVAL, "rank_stride overlaps rank blocks");
+    const int e = launch_assemble_packed(gathered, rank_stride, world, tile_rows, rows_per_rank, W, H, (double*)out,
+                                         hip_stream);
+    if (e) return fail(RT_EDEVICE, "assemble launch: %s", hipGetErrorString((hipError_t)e));
+    return RT_OK;
+}
+
 int rt_gather_async(int world, const int* src_devices, const rt_color* const* locals, int tile_rows,
                     int rows_per_rank, int W, int H, int dst_device, rt_color* out, void* hip_stream)
 {
@@ -131,11 +148,13 @@ int rt_render_gather_async(const rt_scene* scene, const rt_params* params, int t
     const int G = (int)devs.size(), W = params->largeur_image, H = params->hauteur_image;
     // RT_GATHER_RCCL: one rank per device, so the list must not repeat one; the
     // communicators are made (once per list) before anything is enqueued
-    const bool rccl = params->gather == RT_GATHER_RCCL;
+    // (the tests' stand-in library, rt_rccl.h, takes a list that repeats one)
+    const bool packed = (params->gather & RT_GATHER_PACKED_CANVA) != 0;
+    const bool rccl = (params->gather & ~RT_GATHER_PACKED_CANVA) == RT_GATHER_RCCL;
     if (rccl) {
         for (int a = 0; a < G; ++a)
             for (int b = a + 1; b < G; ++b)
-                if (devs[(size_t)a] == devs[(size_t)b])
+                if (devs[(size_t)a] == devs[(size_t)b] && !rccl_ranks_may_share_a_device())
                     return fail(RT_EUNSUPPORTED, "RT_GATHER_RCCL needs distinct devices (rt_init's list names device %d "
                                                  "twice; RCCL has one rank per GPU): use RT_GATHER_PEER", devs[(size_t)a]);
         std::string err;
@@ -148,6 +167,11 @@ int rt_render_gather_async(const rt_scene* scene, const rt_params* params, int t
     int nplanes = 0;
     for (rt_color* o : outs) nplanes += o ? 1 : 0;
     const size_t plane = (size_t)rows_pr * W;                            // colours per plane and slot
+    if (packed && (long long)plane > kPackMaxPixels)
+        return fail(RT_EINVAL, "packed canva: more than 2^30 pixels per slot");
+    // RT_GATHER_PACKED_CANVA: the canva travels as one word per pixel, packed by
+    // its slot; the other nwide requested planes travel as doubles
+    const int nwide = nplanes - (packed ? 1 : 0);
     hipStream_t dst_st = (hipStream_t)hip_stream;
 
     // 1. every slot renders its tiles on its own device and pooled stream,
@@ -161,7 +185,8 @@ int rt_render_gather_async(const rt_scene* scene, const rt_params* params, int t
         HIP_TRY(hipEventRecord(go, dst_st));
     }
     for (int q = 0; q < G && rc == RT_OK; ++q)
-        rc = slots[(size_t)q].render(devs[(size_t)q], scene, params, rt_tiling{0, tile_rows, q, G, n_tiles}, H, outs, go);
+        rc = slots[(size_t)q].render(devs[(size_t)q], scene, params, rt_tiling{0, tile_rows, q, G, n_tiles}, H, outs, go,
+                                     packed);
     // 2. the destination's stream waits for every slot, gathers each plane over
     //    xGMI and un-permutes it; 3. each slot frees its planes after the copies
     if (rc == RT_OK) {
@@ -172,41 +197,75 @@ int rt_render_gather_async(const rt_scene* scene, const rt_params* params, int t
         }
         if (rc == RT_OK) {
             StreamBuffer staging_buf;          // freed on dst_st behind the assembles, before `go` is recorded again
-            const size_t per_slot = rccl ? plane * nplanes : plane;             // colours staged per slot
-            const hipError_t e = staging_buf.alloc((size_t)G * per_slot * sizeof(rt_color), dst_st, dst);
+            // colours staged per slot: RCCL gathers a slot's wide planes in one block, the
+            // peer copies take one plane at a time; the packed words of every slot sit behind
+            const size_t per_slot = rccl ? plane * nwide : nwide ? plane : 0;
+            const size_t wide_bytes = (size_t)G * per_slot * sizeof(rt_color);
+            const hipError_t e = staging_buf.alloc(wide_bytes + (packed ? (size_t)G * plane * sizeof(unsigned) : 0),
+                                                   dst_st, dst);
             if (e != hipSuccess) rc = fail(RT_ENOMEM, "gather staging: %s", hipGetErrorString(e));
             rt_color* staging = (rt_color*)staging_buf.p;
+            unsigned* words = (unsigned*)((char*)staging_buf.p + wide_bytes);
+            const size_t wide0 = packed ? 1 : 0;       // a slot's wide planes start behind its canva when that is packed
             if (rccl && rc == RT_OK) {
-                // every slot's planes (contiguous in its buffer) in one ncclGather to
-                // rank 0, rank 0's part on hip_stream (which waited for its render),
-                // the others' on their own streams after their renders
-                std::vector<const void*> send((size_t)G);
+                // every slot's wide planes (contiguous in its buffer) in one ncclGather to
+                // rank 0, its packed canva in a second one of the same group; rank 0's part
+                // on hip_stream (which waited for its render), the others' on their own
+                // streams after their renders
+                std::vector<GatherPart> parts;
                 std::vector<hipStream_t> sst((size_t)G);
-                for (int q = 0; q < G; ++q) {
-                    send[(size_t)q] = planes_of(q);
-                    sst[(size_t)q] = q == 0 ? dst_st : slots[(size_t)q].stream->st;
+                for (int q = 0; q < G; ++q) sst[(size_t)q] = q == 0 ? dst_st : slots[(size_t)q].stream->st;
+                if (nwide) {
+                    GatherPart w;
+                    for (int q = 0; q < G; ++q) w.send.push_back(planes_of(q) + wide0 * plane);
+                    w.recv = staging;
+                    w.count = per_slot * 3;
+                    parts.push_back(w);
+                }
+                if (packed) {
+                    GatherPart c;
+                    for (int q = 0; q < G; ++q) c.send.push_back(slots[(size_t)q].packed);
+                    c.recv = words;
+                    c.count = plane;
+                    c.words = true;
+                    parts.push_back(c);
                 }
                 std::string err;
-                if (rccl_gather(devs, send, staging, per_slot * 3, sst, err)) rc = fail(RT_EDEVICE, "RCCL: %s", err.c_str());
+                if (rccl_gather(devs, parts, sst, err)) rc = fail(RT_EDEVICE, "RCCL: %s", err.c_str());
             }
-            // the k-th requested plane: assembled from the rank-major staging RCCL
-            // filled, or gathered by peer copies and then assembled
-            int k = 0;
+            // the k-th wide plane: assembled from the rank-major staging RCCL
+            // filled, or gathered by peer copies and then assembled; a packed
+            // canva likewise, by the assemble that widens it
+            size_t k = 0;
             for (int pl = 0; pl < 4 && rc == RT_OK; ++pl) {
                 if (!outs[pl]) continue;
+                if (pl == 0 && packed) {
+                    for (int q = 0; q < G && !rccl && rc == RT_OK; ++q) {
+                        enable_peer(dst, devs[(size_t)q]);
+                        const hipError_t ec = hipMemcpyPeerAsync(words + (size_t)q * plane, dst, slots[(size_t)q].packed,
+                                                                 devs[(size_t)q], plane * sizeof(unsigned), dst_st);
+                        if (ec != hipSuccess)
+                            rc = fail(RT_EDEVICE, "peer copy %d -> %d: %s", devs[(size_t)q], dst, hipGetErrorString(ec));
+                    }
+                    if (rc == RT_OK)
+                        rc = rt_assemble_packed_async(words, (long long)plane, G, tile_rows, rows_pr, W, H, outs[pl], dst_st);
+                    continue;
+                }
                 if (rccl) {
-                    rc = rt_assemble_async(staging + (size_t)k * plane, (long long)per_slot, G, tile_rows, rows_pr, W, H,
+                    rc = rt_assemble_async(staging + k * plane, (long long)per_slot, G, tile_rows, rows_pr, W, H,
                                            outs[pl], dst_st);
                 } else {
                     std::vector<const rt_color*> loc((size_t)G);
-                    for (int q = 0; q < G; ++q) loc[(size_t)q] = planes_of(q) + (size_t)k * plane;
+                    for (int q = 0; q < G; ++q) loc[(size_t)q] = planes_of(q) + (k + wide0) * plane;
                     rc = gather_plane(G, devs.data(), loc.data(), tile_rows, rows_pr, W, H, dst, staging, outs[pl], dst_st);
                 }
                 ++k;
             }
-            if (rc == RT_OK)
+            if (rc == RT_OK) {
                 g_gather_transport = rccl ? "rccl: ncclGather, " + rccl_describe() + ", " + std::to_string(G) + " ranks"
                                           : "peer: hipMemcpyPeerAsync, " + std::to_string(G) + " slots";
+                if (packed) g_gather_transport += ", canva 4 B/px";
+            }
         }
         if (rc == RT_OK) {
             // the slots free their planes only after the copies that read them

@@ -89,15 +89,18 @@ struct RenderSlot {
     Event rendered;          // a gather slot's: recorded behind the render
     StreamBuffer buf;        // the requested planes back to back, `plane` doubles each
     size_t plane = 0;
+    unsigned* packed = nullptr;   // pack_canva: the canva as plane / 3 packed words, behind the planes in buf
 
     // Renders tiling t of the frame, up to row_end, on `device`: cached scene,
     // pooled stream, stream-ordered planes for the non-null entries of
     // want[0..4), launch.  Without `go` this is a host-buffer slot, whose
     // stream is drained when the slot goes.  With it, a gather slot: the
     // stream first waits for go, `rendered` is recorded behind the render,
-    // and the slot goes without waiting for the GPU.
+    // and the slot goes without waiting for the GPU.  pack_canva: the canva
+    // is packed (rt.h "packed canva transport") into `packed` on the same
+    // stream right behind the render, before `rendered`.
     int render(int device, const rt_scene* scene, const rt_params* params, const rt_tiling& t, int row_end,
-               rt_color* const* want, hipEvent_t go);
+               rt_color* const* want, hipEvent_t go, bool pack_canva = false);
 };
 
 }  // namespace rt

@@ -33,6 +33,7 @@ struct Rccl {
     void* h = nullptr;
     std::string path, err;
     int version = 0;
+    bool stub = false;           // the library exports rt_rccl_stub_marker (tests/stubs): ranks may share a device
     decltype(&ncclCommInitAll) comm_init_all = nullptr;
     decltype(&ncclCommDestroy) comm_destroy = nullptr;
     decltype(&ncclGather) gather = nullptr;
@@ -90,6 +91,7 @@ bool load_locked()
     }
     r.h = h;
     r.path = cand;
+    r.stub = dlsym(h, "rt_rccl_stub_marker") != nullptr;
     (void)r.get_version(&r.version);
     return true;
 }
@@ -126,7 +128,13 @@ int rccl_comms(const std::vector<int>& devs, std::string& err)
     return 0;
 }
 
-int rccl_gather(const std::vector<int>& devs, const std::vector<const void*>& send, void* recv, size_t count,
+bool rccl_ranks_may_share_a_device()
+{
+    std::lock_guard<std::mutex> lk(g_rccl_mu);
+    return load_locked() && g_rccl.stub;
+}
+
+int rccl_gather(const std::vector<int>& devs, const std::vector<GatherPart>& parts,
                 const std::vector<hipStream_t>& streams, std::string& err)
 {
     std::lock_guard<std::mutex> lk(g_rccl_mu);
@@ -138,10 +146,12 @@ int rccl_gather(const std::vector<int>& devs, const std::vector<const void*>& se
     (void)hipGetDevice(&prev);
     // one thread drives every rank: the ranks' calls form one group
     ncclResult_t e = g_rccl.group_start();
-    for (size_t q = 0; q < devs.size() && e == ncclSuccess; ++q) {
-        (void)hipSetDevice(devs[q]);
-        e = g_rccl.gather(send[q], q == 0 ? recv : nullptr, count, ncclFloat64, 0, g_comms[q], streams[q]);
-    }
+    for (const GatherPart& p : parts)
+        for (size_t q = 0; q < devs.size() && e == ncclSuccess; ++q) {
+            (void)hipSetDevice(devs[q]);
+            e = g_rccl.gather(p.send[q], q == 0 ? p.recv : nullptr, p.count, p.words ? ncclUint32 : ncclFloat64, 0,
+                              g_comms[q], streams[q]);
+        }
     const ncclResult_t e2 = g_rccl.group_end();
     if (prev >= 0) (void)hipSetDevice(prev);
     if (e != ncclSuccess || e2 != ncclSuccess) {

@@ -7,7 +7,7 @@
  *   rt_demo [-w W] [-s spp] [-b nbRebondMax] [-ao AO_intensity] [-o out.ppm]
  *           [-obj file.obj -mtl file.mtl [-move x y z]] [-devices N]
  *           [-denoise [iterations]] [-vdenoise [iterations]] [-adaptive TOL]
- *           [-queue]
+ *           [-queue] [-packed]
  *
  * -denoise installs the library's built-in a-trous filter (rt_denoise_atrous;
  * not OIDN, and biased: meant for low-spp frames) as the denoiser hook before
@@ -21,6 +21,9 @@
  * adaptive frame filtered with each pixel's own sample count.
  * -queue (with -vdenoise or -adaptive) turns rt_set_accumulate_queue on: their
  * batches take the task-queue kernel; the frame is the same.
+ * -packed turns the packed canva transport on (rt_set_fill_packed_canva and
+ * RT_GATHER_PACKED_CANVA in the params): the canva leaves the device at 4
+ * bytes a pixel; the frame is the same.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -41,7 +44,7 @@ int main(int argc, char** argv)
     int vdenoise = 0;
     rt_vdenoise_params vdn;
     rt_vdenoise_params_init(&vdn);
-    int adaptive = 0, queue = 0;
+    int adaptive = 0, queue = 0, packed = 0;
     rt_adaptive_params adp;
     rt_adaptive_params_init(&adp);
     double AO = 2.5, mx = 0, my = 0, mz = 0;
@@ -66,6 +69,8 @@ int main(int argc, char** argv)
             adp.tolerance = (float)atof(argv[++i]);
         } else if (!strcmp(argv[i], "-queue")) {
             queue = 1;
+        } else if (!strcmp(argv[i], "-packed")) {
+            packed = 1;
         } else if (!strcmp(argv[i], "-move") && i + 3 < argc) {
             mx = atof(argv[++i]);
             my = atof(argv[++i]);
@@ -73,8 +78,9 @@ int main(int argc, char** argv)
         } else {
             fprintf(stderr, "usage: %s [-w W] [-s spp] [-b bounces] [-ao I] [-o out.ppm] "
                             "[-obj f.obj -mtl f.mtl [-move x y z]] [-devices N] [-denoise [iterations]] "
-                            "[-vdenoise [iterations]] [-adaptive TOL] [-queue]\n"
+                            "[-vdenoise [iterations]] [-adaptive TOL] [-queue] [-packed]\n"
                             "  -queue: -vdenoise and -adaptive sample on the task-queue kernel (same frame)\n"
+                            "  -packed: the canva leaves the device at 4 bytes a pixel (same frame)\n"
                             "  -adaptive with -vdenoise: the adaptive frame, filtered with each pixel's own sample count\n",
                     argv[0]);
             return 2;
@@ -141,6 +147,10 @@ int main(int argc, char** argv)
         rt_set_denoise_hook(rt_denoise_atrous);
     }
     if (queue && (vdenoise || adaptive)) rt_set_accumulate_queue(1);
+    if (packed) {
+        rt_set_fill_packed_canva(1);
+        p.gather |= RT_GATHER_PACKED_CANVA;
+    }
     size_t n = (size_t)W * H;
     rt_color* canva = (rt_color*)calloc(n, sizeof(rt_color));
     rt_color* albedo = (rt_color*)calloc(n, sizeof(rt_color));

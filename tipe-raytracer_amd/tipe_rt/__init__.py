@@ -130,6 +130,13 @@ def lib():
             L.rt_set_accumulate_queue.argtypes = [C.c_int]
             L.rt_set_accumulate_queue.restype = C.c_int
             L.rt_last_list_kernel.restype = C.c_char_p
+        if hasattr(L, "rt_canva_pack_async"):            # (added to ABI 5 as well)
+            L.rt_canva_pack_async.argtypes = [C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rt_canva_unpack_async.argtypes = [C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rt_canva_unpack_host.argtypes = [C.c_longlong, C.c_void_p, C.c_void_p]
+            L.rt_assemble_packed_async.argtypes = L.rt_assemble_async.argtypes
+            L.rt_set_fill_packed_canva.argtypes = [C.c_int]
+            L.rt_set_fill_packed_canva.restype = C.c_int
         _lib = L
     return _lib
 
@@ -147,7 +154,9 @@ EXPORTED_SYMBOLS = ["rt_params_init", "rt_init", "rt_shutdown", "rt_last_error",
                     "rt_render_vdenoised", "rt_accumulate_list_async", "rt_adaptive_select_async",
                     "rt_adaptive_workspace_bytes", "rt_adaptive_params_init", "rt_adaptive_async",
                     "rt_resolve_adaptive_async", "rt_render_adaptive", "rt_vdenoise_adaptive_async",
-                    "rt_render_adaptive_vdenoised", "rt_set_accumulate_queue", "rt_last_list_kernel"]
+                    "rt_render_adaptive_vdenoised", "rt_set_accumulate_queue", "rt_last_list_kernel",
+                    "rt_canva_pack_async", "rt_canva_unpack_async", "rt_canva_unpack_host",
+                    "rt_assemble_packed_async", "rt_set_fill_packed_canva"]
 
 # rt_denoise_fn (rt.h): denoiser()'s signature, denoiser.h:31
 DENOISE_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p, Camera, C.c_void_p, C.c_void_p)
@@ -167,6 +176,37 @@ def set_accumulate_queue(enable):
     the task-queue kernel where a render launch would (default off; the sums
     are bit-identical either way).  Returns the previous setting."""
     return bool(lib().rt_set_accumulate_queue(1 if enable else 0))
+
+
+def set_fill_packed_canva(enable):
+    """rt_set_fill_packed_canva (rt.h): render_rows / rt_fill_canva bring the
+    canva to the host at 4 bytes a pixel (default off; the arrays are
+    bit-identical either way).  Returns the previous setting."""
+    return bool(lib().rt_set_fill_packed_canva(1 if enable else 0))
+
+
+def canva_pack_async(n, canva_ptr, packed_ptr, stream=None):
+    """rt_canva_pack_async: n device colours -> n packed words (f0 | f1 << 9 | f2 << 18)."""
+    check(lib().rt_canva_pack_async(n, canva_ptr, packed_ptr, stream))
+
+
+def canva_unpack_async(n, packed_ptr, canva_ptr, stream=None):
+    """rt_canva_unpack_async: n packed words -> n device colours."""
+    check(lib().rt_canva_unpack_async(n, packed_ptr, canva_ptr, stream))
+
+
+def canva_unpack_host(packed):
+    """rt_canva_unpack_host: a uint32 array of packed pixels -> (..., 3) float64 colours, on the host."""
+    w = np.ascontiguousarray(packed, dtype=np.uint32)
+    out = np.zeros(w.shape + (3,))
+    check(lib().rt_canva_unpack_host(w.size, w.ctypes.data, out.ctypes.data))
+    return out
+
+
+def assemble_packed_async(gathered_ptr, world, tile_rows, rows_per_rank, W, H, out_ptr, stream=None, rank_stride=0):
+    """rt_assemble_packed_async: assemble_async on rank-major packed words (rank_stride in pixels)."""
+    check(lib().rt_assemble_packed_async(gathered_ptr, rank_stride, world, tile_rows, rows_per_rank, W, H, out_ptr,
+                                         stream))
 
 
 def last_list_kernel():

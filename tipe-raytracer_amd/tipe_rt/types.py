@@ -49,6 +49,7 @@ RT_SKY_OFF, RT_SKY_LAST_SPHERE = 0, 1
 RT_SEM_MAIN_C, RT_SEM_CUDA = 0, 1
 RT_PREC_FP64, RT_PREC_FP32 = 0, 1
 RT_GATHER_RCCL, RT_GATHER_PEER = 0, 1
+RT_GATHER_PACKED_CANVA = 0x100     # a flag, OR-ed to either transport
 RT_ABI_VERSION = 5
 
 
