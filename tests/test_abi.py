@@ -28,11 +28,48 @@ def exported(lib):
     return {line.split()[-1] for line in out.splitlines() if line.strip()}
 
 
+def declared_params(header):
+    """name -> the parameter declarations of every function the header declares ((void): none)."""
+    src = open(os.path.join(INC, header)).read()
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", src, flags=re.S)
+    src = re.sub(r"static inline[^{;]*\{.*?\n\}", "", src, flags=re.S)
+    out = {}
+    for name, params in re.findall(r"\b(rt_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
+        out[name] = [] if params.strip() == "void" else [" ".join(p.split()) for p in params.split(",")]
+    return out
+
+
+SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong,
+           "size_t": C.c_size_t, "float": C.c_float, "rt_camera": T.Camera}
+
+
+def scalar_of(param):
+    """The ctypes type a by-value parameter must have; None for pointers, arrays and the hook's function pointer."""
+    if "*" in param or "[" in param or param.startswith("rt_denoise_fn"):
+        return None
+    return SCALARS[param.rsplit(" ", 1)[0].replace("const ", "")]
+
+
 def test_rt_h_symbols_exported():
     syms = exported(tipe_rt.LIB_PATH)
     missing = [s for s in declared("rt.h") if s not in syms]
     assert not missing, missing
-    assert set(tipe_rt.EXPORTED_SYMBOLS) <= syms
+    # the ctypes table names exactly the header's functions, each with the header's number of arguments
+    assert sorted(tipe_rt.PROTOTYPES) == declared("rt.h")
+    assert tipe_rt.EXPORTED_SYMBOLS == list(tipe_rt.PROTOTYPES)
+    counts = declared_params("rt.h")
+    assert sorted(counts) == declared("rt.h")          # the two readings of the header agree
+    wrong = {n: (len(args), len(counts[n])) for n, (_, args) in tipe_rt.PROTOTYPES.items() if len(args) != len(counts[n])}
+    assert not wrong, wrong
+    # ... and every by-value argument with the header's type (a long long never goes over as an int); what the
+    # header passes by pointer is a pointer type here
+    for n, (_, args) in tipe_rt.PROTOTYPES.items():
+        for k, (arg, param) in enumerate(zip(args, counts[n])):
+            want = scalar_of(param)
+            if want is not None:
+                assert arg is want, (n, k, param, arg)
+            else:
+                assert arg is C.c_void_p or issubclass(arg, (C._Pointer, C._CFuncPtr)), (n, k, param, arg)
 
 
 def test_host_h_symbols_exported():

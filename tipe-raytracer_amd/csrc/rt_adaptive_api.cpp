@@ -42,27 +42,10 @@ Layout layout_of(long long npx)
     return l;
 }
 
-int validate_frame(int W, int H)
-{
-    if (W < 1 || H < 1) return fail(RT_EINVAL, "adaptive: frame %dx%d", W, H);
-    if ((long long)W * H > (1ll << 30)) return fail(RT_EINVAL, "adaptive: frame %dx%d above 2^30 pixels", W, H);
-    return RT_OK;
-}
-
 int validate_tolerance(float t)
 {
     if (!std::isfinite(t)) return fail(RT_EINVAL, "adaptive: tolerance is not finite");
     if (t < 0x1p-12f || t > 1.0f) return fail(RT_EINVAL, "adaptive: tolerance %g outside [2^-12, 1]", (double)t);
-    return RT_OK;
-}
-
-int validate_workspace(int W, int H, const void* workspace, size_t workspace_bytes)
-{
-    if (!workspace) return fail(RT_EINVAL, "adaptive: workspace is NULL");
-    if ((uintptr_t)workspace % 16) return fail(RT_EINVAL, "adaptive: workspace is not 16-byte aligned");
-    if (workspace_bytes < rt_adaptive_workspace_bytes(W, H))
-        return fail(RT_EINVAL, "adaptive: workspace of %zu bytes, %dx%d needs %zu", workspace_bytes, W, H,
-                    rt_adaptive_workspace_bytes(W, H));
     return RT_OK;
 }
 
@@ -75,6 +58,23 @@ int validate_adaptive(const rt_adaptive_params* a)
     if (((long long)a->first_half << a->max_rounds) > (1ll << 31))   // 2 n_{R-1} = first_half 2^R
         return fail(RT_EINVAL, "adaptive: %d x 2^%d samples per pixel exceed 2^31", a->first_half, a->max_rounds);
     return validate_tolerance(a->tolerance);
+}
+
+// What rt_adaptive_async and the host renders (`entry`) refuse alike.  Yields the params of the schedule's
+// first batch (the caller's nbRayonParPixel is not read) and the frame's size.
+int adaptive_batch(const char* entry, const rt_params* params, const rt_adaptive_params* aparams, rt_params& batch,
+                   int& W, int& H)
+{
+    if (!params) return fail(RT_EINVAL, "params is NULL");
+    int rc;
+    if ((rc = validate_adaptive(aparams))) return rc;
+    batch = *params;
+    batch.nbRayonParPixel = aparams->first_half;
+    if ((rc = validate_params(&batch))) return rc;
+    if (batch.semantics == RT_SEM_CUDA) return fail(RT_EUNSUPPORTED, "%s renders RT_SEM_MAIN_C only", entry);
+    W = batch.largeur_image;
+    H = batch.hauteur_image;
+    return validate_frame_size("adaptive", W, H);
 }
 
 AdaptiveSelect select_args(int W, int H, void* workspace)
@@ -113,110 +113,66 @@ const char* list_queue_name(const RenderPlan& plan)
     return i < 0 ? "none" : names[(size_t)i].c_str();
 }
 
-// Every band of a list launch as plan_list (rt_launch_plan.cpp) sizes them, with
-// its stream-ordered scratch (the uniform block and, for chunks > 1, one band's
-// partials, reused band after band).
+// Every band of a list launch as plan_list (rt_launch_plan.cpp) sizes them (for
+// chunks > 1 the scratch holds one band's partials, reused band after band).
 int launch_list_on_stream(KParams& kp, const double* uni, const unsigned* d_list, const unsigned* d_count,
                           unsigned list_cap, hipStream_t st)
 {
-    const int rc = keep_pool_memory();
-    if (rc) return rc;
+    int rc;
+    if ((rc = keep_pool_memory())) return rc;
     // tree, width and sky -- and, with rt_set_accumulate_queue on, whether a render launch of kp takes the
     // queue and with which pair: the list then takes the queue kernel's list form of that pair (chunks > 1: task_ok)
     const RenderPlan plan = plan_render(kp, false);
     const ListPlan bands = plan_list(kp.chunks, list_cap);
     const unsigned band = bands.band;
-    const size_t partial_bytes = bands.partial_bytes;
-    const bool queue = plan.queue && partial_bytes != 0;
+    const bool queue = plan.queue && bands.partial_bytes != 0;
     t_last_list = queue ? list_queue_name(plan) : plan.wide ? "render_kernel_list_w"
                                               : plan.bvh    ? "render_kernel_list<BVH>"
                                                             : "render_kernel_list";
-    double* d_uni = nullptr;
-    double* d_part = nullptr;
-    // uniform block; for the queue, its task counter on a 64-byte line of its own and the band's task words
-    // on the next (launch_on_stream's layout, rt_internal.h kListTaskOffset)
-    constexpr int kCtr = ((U_COUNT + 7) / 8 + 1) * 8;
-    const size_t words = queue ? (kCtr * sizeof(double) + (kListTaskOffset + kListTaskWords) * sizeof(unsigned) + 7) / 8 : 0;
-    HIP_TRY(hipMallocAsync((void**)&d_uni, std::max<size_t>(U_COUNT, words) * sizeof(double), st));
-    UniBlock ub;
-    for (int i = 0; i < U_COUNT; ++i) ub.v[i] = uni[i];
-    hipError_t e = (hipError_t)launch_set_uniforms(ub, d_uni, st);
-    if (partial_bytes && e == hipSuccess) e = hipMallocAsync((void**)&d_part, partial_bytes, st);
-    kp.uni = d_uni;
-    kp.task_ctr = queue ? (unsigned*)(d_uni + kCtr) : nullptr;
-    kp.stack_cap = plan.stack_cap;
-    ListArgs la = {d_list, d_count, d_part, 0u, 0u, band};
-    for (unsigned long long e0 = 0; e == hipSuccess && e0 < list_cap; e0 += band) {
+    LaunchScratch s;
+    if ((rc = s.open(kp, uni, plan.stack_cap, bands.partial_bytes, queue, st))) return rc;
+    ListArgs la = {d_list, d_count, s.partial, 0u, 0u, band};
+    for (unsigned long long e0 = 0; s.e == hipSuccess && e0 < list_cap; e0 += band) {
         la.e0 = (unsigned)e0;
         la.e1 = (unsigned)std::min<unsigned long long>(e0 + band, list_cap);
-        e = (hipError_t)(queue ? launch_render_list_queue(kp, plan, la, st) : launch_render_list(kp, plan, la, st));
+        s.e = (hipError_t)(queue ? launch_render_list_queue(kp, plan, la, st) : launch_render_list(kp, plan, la, st));
     }
-    if (d_part) (void)hipFreeAsync(d_part, st);
-    (void)hipFreeAsync(d_uni, st);
-    if (e != hipSuccess) return fail(RT_EDEVICE, "list render launch: %s", hipGetErrorString(e));
-    return RT_OK;
+    return s.result("list render");
 }
 
 // rt_render_adaptive (filter false: the planes are rt_resolve_adaptive_async's, vparams is not read) and
-// rt_render_adaptive_vdenoised (the planes are rt_vdenoise_adaptive_async's): the loop on rt_init's first
-// device with the cached scene, a pooled stream and pinned staging; copies out only on success.  `what`
+// rt_render_adaptive_vdenoised (the planes are rt_vdenoise_adaptive_async's) as one HostFrameJob.  `what`
 // names the entry point in messages.
 int render_adaptive_host(const char* what, const rt_scene* scene, const rt_params* params,
                          const rt_adaptive_params* aparams, const rt_vdenoise_params* vparams, bool filter,
                          rt_color* canva, rt_color* albedo, rt_color* normal, int* rounds)
 {
-    int rc, dev;
-    if ((rc = validate_scene(scene))) return rc;
-    if (!params) return fail(RT_EINVAL, "params is NULL");
-    if ((rc = validate_adaptive(aparams))) return rc;
-    rt_params batch = *params;
-    batch.nbRayonParPixel = aparams->first_half;
-    if ((rc = validate_params(&batch))) return rc;
-    if (batch.semantics == RT_SEM_CUDA) return fail(RT_EUNSUPPORTED, "%s renders RT_SEM_MAIN_C only", what);
-    const int W = batch.largeur_image, H = batch.hauteur_image;
-    if ((rc = validate_frame(W, H))) return rc;
+    rt_params batch;
+    int rc, W, H;
+    if ((rc = validate_scene(scene)) || (rc = adaptive_batch(what, params, aparams, batch, W, H))) return rc;
     if (filter && (rc = validate_vdenoise(W, H, vparams))) return rc;
     if (!canva) return fail(RT_EINVAL, "adaptive: canva is NULL");
-    if ((rc = first_device(dev))) return rc;
-    std::shared_ptr<rt_device_scene> sc;
-    if ((rc = scene_cache_get(dev, scene, sc))) return rc;
-    StreamLease ps;                  // drained on every return: the caller reads canva next
-    if ((rc = ps.acquire(dev, true))) return rc;
-    DeviceGuard g(dev);
     const size_t npx = (size_t)W * H, plane = npx * sizeof(rt_color), sums = npx * 9 * sizeof(double);
     const size_t rbytes = (npx * sizeof(int) + 15) / 16 * 16, aws_bytes = rt_adaptive_workspace_bytes(W, H);
     // the filter runs behind the loop on the same stream: one workspace serves both, the larger one's size
     const size_t vws_bytes = filter ? rt_vdenoise_workspace_bytes(W, H) : 0;
     const size_t ws_bytes = (std::max(aws_bytes, vws_bytes) + 15) / 16 * 16;
-    rt_color* const dst[3] = {canva, albedo, normal};
-    StreamBuffer dbuf;               // device: the two accumulators, the workspace, the round counts, the planes
-    hipError_t e = ps->reserve_host(3 * plane + rbytes);
-    if (e == hipSuccess) e = dbuf.alloc(2 * sums + ws_bytes + rbytes + 3 * plane, ps->st, dev);
-    if (e != hipSuccess) return fail(RT_ENOMEM, "adaptive buffers: %s", hipGetErrorString(e));
-    char* buf = (char*)dbuf.p;
-    double* acc[2] = {(double*)buf, (double*)(buf + sums)};
-    char* ws = buf + 2 * sums;
-    int* d_rounds = (int*)(ws + ws_bytes);
-    char* planes = ws + ws_bytes + rbytes;
-    const rt_frame fr = {(rt_color*)planes, albedo ? (rt_color*)(planes + plane) : nullptr,
-                         normal ? (rt_color*)(planes + 2 * plane) : nullptr, nullptr};
-    if ((rc = rt_adaptive_async(sc.get(), params, aparams, acc[0], acc[1], d_rounds, ws, aws_bytes,
-                                filter ? nullptr : &fr, ps->st)))
+    HostFrameJob job;
+    if ((rc = job.open("adaptive", scene, 3 * plane + rbytes, 2 * sums + ws_bytes + rbytes + 3 * plane))) return rc;
+    double* acc0 = (double*)job.take(2 * sums);           // the two accumulators, back to back
+    double* acc1 = (double*)((char*)acc0 + sums);
+    char* ws = job.take(ws_bytes);
+    int* d_rounds = (int*)job.take(rbytes);
+    rt_color* planes = (rt_color*)job.take(3 * plane);
+    const rt_frame fr = {planes, albedo ? planes + npx : nullptr, normal ? planes + 2 * npx : nullptr, nullptr};
+    if ((rc = rt_adaptive_async(job.scene(), params, aparams, acc0, acc1, d_rounds, ws, aws_bytes,
+                                filter ? nullptr : &fr, job.stream())))
         return rc;
-    if (filter && (rc = rt_vdenoise_adaptive_async(W, H, acc[0], acc[1], d_rounds, aparams->first_half, vparams, ws,
-                                                   vws_bytes, &fr, ps->st)))
+    if (filter && (rc = rt_vdenoise_adaptive_async(W, H, acc0, acc1, d_rounds, aparams->first_half, vparams, ws,
+                                                   vws_bytes, &fr, job.stream())))
         return rc;
-    char* host = (char*)ps->host;
-    for (int pl = 0; pl < 3 && e == hipSuccess; ++pl)
-        if (dst[pl]) e = hipMemcpyAsync(host + pl * plane, planes + pl * plane, plane, hipMemcpyDeviceToHost, ps->st);
-    if (rounds && e == hipSuccess)
-        e = hipMemcpyAsync(host + 3 * plane, d_rounds, npx * sizeof(int), hipMemcpyDeviceToHost, ps->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(ps->st);
-    if (e != hipSuccess) return fail(RT_EDEVICE, "adaptive: %s", hipGetErrorString(e));
-    for (int pl = 0; pl < 3; ++pl)
-        if (dst[pl]) std::memcpy(dst[pl], host + pl * plane, plane);
-    if (rounds) std::memcpy(rounds, host + 3 * plane, npx * sizeof(int));
-    return RT_OK;
+    return job.finish({{canva, planes, plane}, {albedo, planes + npx, plane}, {normal, planes + 2 * npx, plane},
+                       {rounds, d_rounds, npx * sizeof(int)}});
 }
 
 }  // namespace
@@ -236,9 +192,7 @@ int rt_accumulate_list_async(const rt_device_scene* scene, const rt_params* para
     const unsigned long long npx = (unsigned long long)params->largeur_image * (unsigned long long)params->hauteur_image;
     if (list_cap == 0 || list_cap > npx)
         return fail(RT_EINVAL, "list_cap %u outside 1..%llu (the frame's pixels)", list_cap, npx);
-    if (sample_offset < 0 || sample_offset + params->nbRayonParPixel > (1ll << 32))
-        return fail(RT_EINVAL, "samples [%lld, %lld) exceed the 32-bit Philox sample word", sample_offset,
-                    sample_offset + params->nbRayonParPixel);
+    if ((rc = validate_sample_window(sample_offset, params->nbRayonParPixel))) return rc;
     const rt_tiling whole = {0, params->hauteur_image, 0, 1, 1};
     KParams kp;
     double uni[U_COUNT];
@@ -253,7 +207,7 @@ const char* rt_last_list_kernel(void) { return t_last_list; }
 
 size_t rt_adaptive_workspace_bytes(int W, int H)
 {
-    if (W < 1 || H < 1 || (long long)W * H > (1ll << 30)) return 0;
+    if (!frame_size_ok(W, H)) return 0;
     return layout_of((long long)W * H).total;
 }
 
@@ -262,12 +216,14 @@ int rt_adaptive_select_async(int W, int H, const double* d_sums_a, const double*
                              void* workspace, size_t workspace_bytes, void* hip_stream)
 {
     int rc;
-    if ((rc = validate_frame(W, H))) return rc;
+    if ((rc = validate_frame_size("adaptive", W, H))) return rc;
     if (!d_sums_a || !d_sums_b) return fail(RT_EINVAL, "adaptive: an accumulator is NULL");
     if (!d_list || !d_count || !d_rounds) return fail(RT_EINVAL, "adaptive: d_list, d_count or d_rounds is NULL");
     if (n_half < 1) return fail(RT_EINVAL, "adaptive: n_half %d < 1", n_half);
     if (round < 0 || round > 15) return fail(RT_EINVAL, "adaptive: round %d outside 0..15", round);
-    if ((rc = validate_tolerance(tolerance)) || (rc = validate_workspace(W, H, workspace, workspace_bytes))) return rc;
+    if ((rc = validate_tolerance(tolerance)) ||
+        (rc = validate_workspace("adaptive", W, H, workspace, workspace_bytes, rt_adaptive_workspace_bytes(W, H))))
+        return rc;
     AdaptiveSelect s = select_args(W, H, workspace);
     s.all = round == 0;
     s.sums_a = d_sums_a;
@@ -292,7 +248,7 @@ int rt_resolve_adaptive_async(int W, int H, const double* d_sums_a, const double
                               int first_half, const rt_frame* frame, void* hip_stream)
 {
     int rc;
-    if ((rc = validate_frame(W, H))) return rc;
+    if ((rc = validate_frame_size("adaptive", W, H))) return rc;
     if (!d_sums_a || !d_sums_b) return fail(RT_EINVAL, "adaptive: an accumulator is NULL");
     if (!d_rounds) return fail(RT_EINVAL, "adaptive: d_rounds is NULL");
     if (first_half < 1) return fail(RT_EINVAL, "adaptive: first_half %d < 1", first_half);
@@ -309,18 +265,13 @@ int rt_adaptive_async(const rt_device_scene* scene, const rt_params* params, con
                       const rt_frame* frame, void* hip_stream)
 {
     if (!scene) return fail(RT_EINVAL, "scene is NULL");
-    if (!params) return fail(RT_EINVAL, "params is NULL");
-    int rc;
-    if ((rc = validate_adaptive(aparams))) return rc;
-    rt_params batch = *params;                   // nbRayonParPixel is the schedule's, not the caller's
-    batch.nbRayonParPixel = aparams->first_half;
-    if ((rc = validate_params(&batch))) return rc;
-    if (batch.semantics == RT_SEM_CUDA) return fail(RT_EUNSUPPORTED, "rt_adaptive_async renders RT_SEM_MAIN_C only");
-    const int W = batch.largeur_image, H = batch.hauteur_image;
-    if ((rc = validate_frame(W, H))) return rc;
+    rt_params batch;                             // nbRayonParPixel is the schedule's, not the caller's
+    int rc, W, H;
+    if ((rc = adaptive_batch("rt_adaptive_async", params, aparams, batch, W, H))) return rc;
     if (!d_sums_a || !d_sums_b) return fail(RT_EINVAL, "adaptive: an accumulator is NULL");
     if (!d_rounds) return fail(RT_EINVAL, "adaptive: d_rounds is NULL");
-    if ((rc = validate_workspace(W, H, workspace, workspace_bytes))) return rc;
+    if ((rc = validate_workspace("adaptive", W, H, workspace, workspace_bytes, rt_adaptive_workspace_bytes(W, H))))
+        return rc;
     if (frame && !frame->canva) return fail(RT_EINVAL, "adaptive: frame.canva is NULL");
 
     const hipStream_t st = (hipStream_t)hip_stream;

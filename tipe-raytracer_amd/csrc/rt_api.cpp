@@ -1,9 +1,10 @@
 // rt_api.cpp — C-ABI of librt_hip.so (include/rt/rt.h): validation, init,
 // scene upload into the HBM layout of rt_internal.h (prepared on the host by
-// rt_scene_prep.cpp), launches (descriptor and plan: rt_launch_plan.cpp) and
-// the single-device async entry points.  The host-buffer drop-ins are in
-// rt_drop_in.cpp, the multi-device gather in rt_gather.cpp, the denoiser's entry points in rt_denoise_api.cpp,
-// the diagnostics in rt_diag.cpp.
+// rt_scene_prep.cpp), launches (plan: rt_launch_plan.cpp; scratch: LaunchScratch),
+// the refusals that several files share and the single-device async entry points.
+// The host-buffer drop-ins are in rt_drop_in.cpp, the multi-device gather in
+// rt_gather.cpp, the denoisers' entry points in rt_denoise_api.cpp, adaptive
+// sampling's in rt_adaptive_api.cpp, the diagnostics in rt_diag.cpp.
 // Every HIP call is checked; failures return RT_E* and set rt_last_error().
 #include <atomic>
 #include <cstdarg>
@@ -167,34 +168,63 @@ int keep_pool_memory()
     return RT_OK;
 }
 
-// One render or count run of kp as plan_render lays it out, with its stream-
-// ordered scratch (uniform block, the chunk partials of one band).
-int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count)
+bool frame_size_ok(int W, int H) { return W >= 1 && H >= 1 && (long long)W * H <= (1ll << 30); }
+
+int validate_frame_size(const char* what, int W, int H)
 {
-    const int rc = keep_pool_memory();
-    if (rc) return rc;
-    const RenderPlan plan = plan_render(kp, count);     // kernel, stack and bands, decided once
-    double* d_uni = nullptr;
-    double* d_part = nullptr;
-    // uniform block + render_kernel_q's task counter (on its own 64-byte line)
-    HIP_TRY(hipMallocAsync((void**)&d_uni, (U_COUNT + 16) * sizeof(double), st));
+    if (W < 1 || H < 1) return fail(RT_EINVAL, "%s: frame %dx%d", what, W, H);
+    if (!frame_size_ok(W, H)) return fail(RT_EINVAL, "%s: frame %dx%d above 2^30 pixels", what, W, H);
+    return RT_OK;
+}
+
+int validate_workspace(const char* what, int W, int H, const void* workspace, size_t workspace_bytes, size_t need)
+{
+    if (!workspace) return fail(RT_EINVAL, "%s: workspace is NULL", what);
+    if ((uintptr_t)workspace % 16) return fail(RT_EINVAL, "%s: workspace is not 16-byte aligned", what);
+    if (workspace_bytes < need)
+        return fail(RT_EINVAL, "%s: workspace of %zu bytes, %dx%d needs %zu", what, workspace_bytes, W, H, need);
+    return RT_OK;
+}
+
+int validate_sample_window(long long sample_offset, int S)
+{
+    if (sample_offset < 0 || sample_offset + S > (1ll << 32))
+        return fail(RT_EINVAL, "samples [%lld, %lld) exceed the 32-bit Philox sample word", sample_offset,
+                    sample_offset + S);
+    return RT_OK;
+}
+
+int LaunchScratch::open(KParams& kp, const double* uni, int stack_cap, size_t partial_bytes, bool queue,
+                        hipStream_t stream)
+{
+    st = stream;
+    HIP_TRY(hipMallocAsync((void**)&block, kLaunchScratchBytes, st));
     UniBlock ub;
     for (int i = 0; i < U_COUNT; ++i) ub.v[i] = uni[i];
-    hipError_t e = (hipError_t)launch_set_uniforms(ub, d_uni, st);
-    if (plan.partial_bytes && e == hipSuccess) e = hipMallocAsync((void**)&d_part, plan.partial_bytes, st);
-    kp.uni = d_uni;
-    kp.partial = d_part;
-    kp.task_ctr = (d_part && plan.task_ok) ? (unsigned*)(d_uni + ((U_COUNT + 7) / 8 + 1) * 8) : nullptr;
-    kp.stack_cap = plan.stack_cap;
-    kp.band_rows = plan.band_rows;
-    for (int y0 = 0; e == hipSuccess && y0 < kp.local_rows; y0 += plan.band_rows) {
-        kp.band_y0 = y0;
-        e = (hipError_t)(count ? launch_count(kp, plan, st) : launch_render(kp, plan, st));
-    }
-    if (d_part) (void)hipFreeAsync(d_part, st);
-    (void)hipFreeAsync(d_uni, st);
-    if (e != hipSuccess) return fail(RT_EDEVICE, "render launch: %s", hipGetErrorString(e));
+    e = (hipError_t)launch_set_uniforms(ub, block, st);
+    if (partial_bytes && e == hipSuccess) e = hipMallocAsync((void**)&partial, partial_bytes, st);
+    kp.uni = block;
+    kp.task_ctr = (partial && queue) ? (unsigned*)(block + kTaskCtrDouble) : nullptr;
+    kp.stack_cap = stack_cap;
     return RT_OK;
+}
+
+// One render or count run of kp as plan_render lays it out, band by band (the
+// scratch holds the chunk partials of one band).
+int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count)
+{
+    int rc;
+    if ((rc = keep_pool_memory())) return rc;
+    const RenderPlan plan = plan_render(kp, count);     // kernel, stack and bands, decided once
+    LaunchScratch s;
+    if ((rc = s.open(kp, uni, plan.stack_cap, plan.partial_bytes, plan.task_ok, st))) return rc;
+    kp.partial = s.partial;
+    kp.band_rows = plan.band_rows;
+    for (int y0 = 0; s.e == hipSuccess && y0 < kp.local_rows; y0 += plan.band_rows) {
+        kp.band_y0 = y0;
+        s.e = (hipError_t)(count ? launch_count(kp, plan, st) : launch_render(kp, plan, st));
+    }
+    return s.result("render");
 }
 
 // What the scene-taking entry points do once their arguments are checked: the
@@ -340,9 +370,7 @@ int rt_accumulate_async(const rt_device_scene* scene, const rt_params* params, l
     int rc;
     if ((rc = validate_params(params)) || (rc = validate_tiling(tiling))) return rc;
     if (!d_sums) return fail(RT_EINVAL, "d_sums is NULL");
-    if (sample_offset < 0 || sample_offset + params->nbRayonParPixel > (1ll << 32))
-        return fail(RT_EINVAL, "samples [%lld, %lld) exceed the 32-bit Philox sample word", sample_offset,
-                    sample_offset + params->nbRayonParPixel);
+    if ((rc = validate_sample_window(sample_offset, params->nbRayonParPixel))) return rc;
     return launch_scene(scene, params, tiling, hip_stream, false, [&](KParams& kp) {
         kp.sums = d_sums;
         kp.s_base = sample_offset;

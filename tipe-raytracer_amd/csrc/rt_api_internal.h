@@ -1,7 +1,8 @@
 // rt_api_internal.h — what the C-ABI's files (rt_api.cpp, rt_drop_in.cpp,
-// rt_gather.cpp, rt_denoise_api.cpp, rt_diag.cpp) share: error reporting, the
-// device list, owning device memory and the uploaded scene.  What a drop-in
-// holds while it runs (streams, buffers, slots) is in rt_host_slots.h.
+// rt_gather.cpp, rt_denoise_api.cpp, rt_adaptive_api.cpp, rt_diag.cpp) share:
+// error reporting, the device list, the refusals, owning device memory, a
+// launch's scratch and the uploaded scene.  What a drop-in holds while it runs
+// (streams, buffers, slots, the whole-frame job) is in rt_host_slots.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,14 +41,17 @@ struct DeviceGuard {
     }
 };
 
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy&) = delete;
+    NoCopy& operator=(const NoCopy&) = delete;
+};
+
 // Device memory that is freed with its owner (on the device that is current
 // then).  Null until alloc/upload; an empty upload leaves it null.
 template <class T>
-struct DevArray {
+struct DevArray : NoCopy {
     T* p = nullptr;
-    DevArray() = default;
-    DevArray(const DevArray&) = delete;
-    DevArray& operator=(const DevArray&) = delete;
     ~DevArray() { (void)hipFree(p); }
     operator T*() const { return p; }
     hipError_t alloc(size_t n) { return hipMalloc((void**)&p, n * sizeof(T)); }
@@ -68,6 +72,14 @@ int validate_scene(const rt_scene* sc);
 int validate_params(const rt_params* p);
 int validate_vdenoise(int W, int H, const rt_vdenoise_params* p);    // rt_denoise_api.cpp: the frame size too
 
+// What adaptive sampling and the two denoisers refuse alike; `what` is the caller's prefix ("adaptive",
+// "denoise", "vdenoise").  A frame: W, H >= 1 and at most 2^30 pixels.  A workspace: not NULL, 16-byte aligned,
+// `need` bytes, checked in that order.  A sample window: [offset, offset + S) within the 32-bit Philox word.
+bool frame_size_ok(int W, int H);
+int validate_frame_size(const char* what, int W, int H);
+int validate_workspace(const char* what, int W, int H, const void* workspace, size_t workspace_bytes, size_t need);
+int validate_sample_window(long long sample_offset, int S);
+
 // rt_launch_plan.h's fill_kparams on an uploaded scene, with rt_set_zero_throughput_exit's switch;
 // launch_on_stream plans the launch (plan_render) and runs its bands.
 // keep_pool_memory: the launches' stream-ordered scratch stays mapped between calls (once per device).
@@ -75,6 +87,26 @@ void fill_kparams(const rt_device_scene* sc, const rt_params* p, const rt_tiling
 int keep_pool_memory();
 int launch_on_stream(KParams& kp, const double* uni, hipStream_t st, bool count);
 void free_scene(rt_device_scene* s);
+
+// The stream-ordered scratch of one launch, dense (launch_on_stream) or listed (rt_adaptive_api.cpp): one block
+// in rt_internal.h's layout (kLaunchScratchBytes) with the uniforms uploaded, and one band's partials when
+// partial_bytes is not 0.  open sets kp.uni, kp.stack_cap and kp.task_ctr (the block's counter when there are
+// partials and `queue` holds, else null); the caller runs its bands while e is hipSuccess, keeps the first
+// failure in e and returns result().  Both blocks are freed in stream order when the scratch goes.
+struct LaunchScratch : NoCopy {
+    double* block = nullptr;
+    double* partial = nullptr;
+    hipStream_t st = nullptr;
+    hipError_t e = hipSuccess;
+    ~LaunchScratch()
+    {
+        if (partial) (void)hipFreeAsync(partial, st);
+        if (block) (void)hipFreeAsync(block, st);
+    }
+    // RT_E* when the block itself could not be had (nothing was enqueued); a later failure is in e
+    int open(KParams& kp, const double* uni, int stack_cap, size_t partial_bytes, bool queue, hipStream_t stream);
+    int result(const char* what) const { return e == hipSuccess ? RT_OK : fail(RT_EDEVICE, "%s launch: %s", what, hipGetErrorString(e)); }
+};
 
 // rt_drop_in.cpp, for rt_shutdown
 int scene_cache_clear();

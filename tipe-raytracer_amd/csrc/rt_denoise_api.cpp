@@ -8,7 +8,6 @@
 // (rt_render_vdenoised).
 #include <atomic>
 #include <cmath>
-#include <cstring>
 #include <mutex>
 
 #include "rt_host_slots.h"
@@ -23,14 +22,7 @@ std::atomic<rt_denoise_fn> g_denoise{nullptr};
 std::mutex g_denoise_mu;
 rt_denoise_params g_denoise_params = kDefaults;    // rt_denoise_atrous's
 
-// what the two denoisers validate alike: the frame size, then the pass count and the three sigmas
-int validate_frame_size(int W, int H)
-{
-    if (W < 1 || H < 1) return fail(RT_EINVAL, "denoise: frame %dx%d", W, H);
-    if ((long long)W * H > (1ll << 30)) return fail(RT_EINVAL, "denoise: frame %dx%d above 2^30 pixels", W, H);
-    return RT_OK;
-}
-
+// what the two denoisers validate alike behind the frame size: the pass count and the three sigmas
 int validate_passes(int iterations, int min_iterations, const float* sig, const char* const* name)
 {
     if (iterations < min_iterations || iterations > 8)
@@ -46,7 +38,7 @@ int validate_passes(int iterations, int min_iterations, const float* sig, const 
 // frame size and parameters of the built-in denoiser
 int validate_denoise(int W, int H, const rt_denoise_params* p)
 {
-    const int rc = validate_frame_size(W, H);
+    const int rc = validate_frame_size("denoise", W, H);
     if (rc) return rc;
     if (!p) return fail(RT_EINVAL, "denoise: params is NULL");
     const float sig[3] = {p->sigma_color, p->sigma_normal, p->sigma_albedo};
@@ -61,7 +53,7 @@ constexpr rt_vdenoise_params kVDefaults = {4, 4.0f, 0.5f, 0.25f};
 // ... and of the variance-guided one (rt_adaptive_api.cpp validates with it too)
 int rt::validate_vdenoise(int W, int H, const rt_vdenoise_params* p)
 {
-    const int rc = validate_frame_size(W, H);
+    const int rc = validate_frame_size("denoise", W, H);
     if (rc) return rc;
     if (!p) return fail(RT_EINVAL, "vdenoise: params is NULL");
     const float sig[3] = {p->sigma_luminance, p->sigma_normal, p->sigma_albedo};
@@ -77,16 +69,13 @@ int vdenoise_on_stream(int W, int H, const double* d_sums_a, const double* d_sum
                        const char* n_name, const rt_vdenoise_params* params, void* workspace, size_t workspace_bytes,
                        const rt_frame* out, void* hip_stream)
 {
-    const int rc = validate_vdenoise(W, H, params);
+    int rc = validate_vdenoise(W, H, params);
     if (rc) return rc;
     if (!d_sums_a || !d_sums_b) return fail(RT_EINVAL, "vdenoise: an accumulator is NULL");
     if (n < 1) return fail(RT_EINVAL, "vdenoise: %s %d < 1", n_name, n);
     if (!out || !out->canva) return fail(RT_EINVAL, "vdenoise: out.canva is NULL");
-    if (!workspace) return fail(RT_EINVAL, "vdenoise: workspace is NULL");
-    if ((uintptr_t)workspace % 16) return fail(RT_EINVAL, "vdenoise: workspace is not 16-byte aligned");
-    if (workspace_bytes < rt_vdenoise_workspace_bytes(W, H))
-        return fail(RT_EINVAL, "vdenoise: workspace of %zu bytes, %dx%d needs %zu", workspace_bytes, W, H,
-                    rt_vdenoise_workspace_bytes(W, H));
+    if ((rc = validate_workspace("vdenoise", W, H, workspace, workspace_bytes, rt_vdenoise_workspace_bytes(W, H))))
+        return rc;
     const int e = launch_vdenoise(W, H, d_sums_a, d_sums_b, d_rounds, n, params->iterations, params->sigma_luminance,
                                   params->sigma_normal, params->sigma_albedo, (float*)workspace, (double*)out->canva,
                                   (double*)out->albedo, (double*)out->normal, (double*)out->radiance, hip_stream);
@@ -144,21 +133,18 @@ void rt_denoise_params_init(rt_denoise_params* p)
 
 size_t rt_denoise_workspace_bytes(int W, int H)
 {
-    if (W < 1 || H < 1 || (long long)W * H > (1ll << 30)) return 0;
+    if (!frame_size_ok(W, H)) return 0;
     return 4 * denoise_plane_floats((long long)W * H) * sizeof(float);
 }
 
 int rt_denoise_async(int W, int H, const rt_frame* frame, const rt_denoise_params* params, void* workspace,
                      size_t workspace_bytes, float* color3_out, void* hip_stream)
 {
-    const int rc = validate_denoise(W, H, params);
+    int rc = validate_denoise(W, H, params);
     if (rc) return rc;
     if (!frame || !frame->canva) return fail(RT_EINVAL, "denoise: canva is NULL");
-    if (!workspace) return fail(RT_EINVAL, "denoise: workspace is NULL");
-    if ((uintptr_t)workspace % 16) return fail(RT_EINVAL, "denoise: workspace is not 16-byte aligned");
-    if (workspace_bytes < rt_denoise_workspace_bytes(W, H))
-        return fail(RT_EINVAL, "denoise: workspace of %zu bytes, %dx%d needs %zu", workspace_bytes, W, H,
-                    rt_denoise_workspace_bytes(W, H));
+    if ((rc = validate_workspace("denoise", W, H, workspace, workspace_bytes, rt_denoise_workspace_bytes(W, H))))
+        return rc;
     const int e = launch_denoise(W, H, (double*)frame->canva, (const double*)frame->albedo,
                                  (const double*)frame->normal, params->iterations, params->sigma_color,
                                  params->sigma_normal, params->sigma_albedo, (float*)workspace, color3_out, hip_stream);
@@ -169,36 +155,21 @@ int rt_denoise_async(int W, int H, const rt_frame* frame, const rt_denoise_param
 int rt_denoise_host(int W, int H, rt_color* canva, const rt_color* albedo, const rt_color* normal,
                     const rt_denoise_params* params)
 {
-    int rc, dev;
+    int rc;
     if ((rc = validate_denoise(W, H, params))) return rc;
     if (!canva) return fail(RT_EINVAL, "denoise: canva is NULL");
-    if ((rc = first_device(dev))) return rc;
-    StreamLease ps;                  // drained on every return: the caller reads canva next
-    if ((rc = ps.acquire(dev, true))) return rc;
-    DeviceGuard g(dev);
-    const size_t plane = (size_t)W * H * sizeof(rt_color), ws_bytes = rt_denoise_workspace_bytes(W, H);
+    const size_t npx = (size_t)W * H, plane = npx * sizeof(rt_color), ws_bytes = rt_denoise_workspace_bytes(W, H);
+    HostFrameJob job;
+    if ((rc = job.open("denoise", nullptr, 3 * plane, ws_bytes + 3 * plane))) return rc;
+    char* ws = job.take(ws_bytes);
+    rt_color* planes = (rt_color*)job.take(3 * plane);
+    const rt_frame fr = {planes, albedo ? planes + npx : nullptr, normal ? planes + 2 * npx : nullptr, nullptr};
     const rt_color* src[3] = {canva, albedo, normal};
-    StreamBuffer dbuf;               // device: the workspace, then the given planes
-    hipError_t e = ps->reserve_host(3 * plane);
-    if (e == hipSuccess) e = dbuf.alloc(ws_bytes + 3 * plane, ps->st, dev);
-    if (e != hipSuccess) return fail(RT_ENOMEM, "denoise buffers: %s", hipGetErrorString(e));
-    char* buf = (char*)dbuf.p;
-    rt_frame fr = {nullptr, nullptr, nullptr, nullptr};
-    rt_color** dst[3] = {&fr.canva, &fr.albedo, &fr.normal};
-    for (int pl = 0; pl < 3 && e == hipSuccess; ++pl) {
-        if (!src[pl]) continue;
-        char* host = (char*)ps->host + pl * plane;
-        std::memcpy(host, src[pl], plane);
-        *dst[pl] = (rt_color*)(buf + ws_bytes + pl * plane);
-        e = hipMemcpyAsync(*dst[pl], host, plane, hipMemcpyHostToDevice, ps->st);
-    }
-    if (e != hipSuccess) return fail(RT_EDEVICE, "denoise upload: %s", hipGetErrorString(e));
-    if ((rc = rt_denoise_async(W, H, &fr, params, buf, ws_bytes, nullptr, ps->st))) return rc;
-    e = hipMemcpyAsync(ps->host, fr.canva, plane, hipMemcpyDeviceToHost, ps->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(ps->st);
-    if (e != hipSuccess) return fail(RT_EDEVICE, "denoise: %s", hipGetErrorString(e));
-    std::memcpy(canva, ps->host, plane);
-    return RT_OK;
+    rt_color* const dst[3] = {fr.canva, fr.albedo, fr.normal};
+    for (int pl = 0; pl < 3; ++pl)
+        if (src[pl] && (rc = job.upload(dst[pl], src[pl], plane))) return rc;
+    if ((rc = rt_denoise_async(W, H, &fr, params, ws, ws_bytes, nullptr, job.stream()))) return rc;
+    return job.finish({{canva, fr.canva, plane}});
 }
 
 int rt_set_denoise_params(const rt_denoise_params* params)
@@ -229,7 +200,7 @@ void rt_vdenoise_params_init(rt_vdenoise_params* p)
 
 size_t rt_vdenoise_workspace_bytes(int W, int H)
 {
-    if (W < 1 || H < 1 || (long long)W * H > (1ll << 30)) return 0;
+    if (!frame_size_ok(W, H)) return 0;
     const long long npx = (long long)W * H;
     return (4 * denoise_plane_floats(npx) + 3 * vdenoise_scalar_floats(npx)) * sizeof(float);
 }
@@ -254,47 +225,33 @@ int rt_vdenoise_adaptive_async(int W, int H, const double* d_sums_a, const doubl
 int rt_render_vdenoised(const rt_scene* scene, const rt_params* params, const rt_vdenoise_params* vparams,
                         rt_color* canva, rt_color* albedo, rt_color* normal)
 {
-    int rc, dev;
+    int rc;
     if ((rc = validate_scene(scene)) || (rc = validate_params(params))) return rc;
     const int W = params->largeur_image, H = params->hauteur_image, S = params->nbRayonParPixel;
     if ((rc = validate_vdenoise(W, H, vparams))) return rc;
     if (!canva) return fail(RT_EINVAL, "vdenoise: canva is NULL");
     if (S < 2 || S % 2) return fail(RT_EINVAL, "vdenoise: nbRayonParPixel %d is not even and >= 2", S);
-    if ((rc = first_device(dev))) return rc;
-    std::shared_ptr<rt_device_scene> sc;
-    if ((rc = scene_cache_get(dev, scene, sc))) return rc;
-    StreamLease ps;                  // drained on every return: the caller reads canva next
-    if ((rc = ps.acquire(dev, true))) return rc;
-    DeviceGuard g(dev);
     const size_t npx = (size_t)W * H, plane = npx * sizeof(rt_color), sums = npx * 9 * sizeof(double);
     const size_t ws_bytes = rt_vdenoise_workspace_bytes(W, H);
-    rt_color* const dst[3] = {canva, albedo, normal};
-    StreamBuffer dbuf;               // device: the two accumulators, the workspace, then the output planes
-    hipError_t e = ps->reserve_host(3 * plane);
-    if (e == hipSuccess) e = dbuf.alloc(2 * sums + ws_bytes + 3 * plane, ps->st, dev);
-    if (e != hipSuccess) return fail(RT_ENOMEM, "vdenoise buffers: %s", hipGetErrorString(e));
-    char* buf = (char*)dbuf.p;
-    double* acc[2] = {(double*)buf, (double*)(buf + sums)};
-    char* planes = buf + 2 * sums + ws_bytes;
-    if ((e = hipMemsetAsync(buf, 0, 2 * sums, ps->st)) != hipSuccess)
-        return fail(RT_EDEVICE, "vdenoise clear: %s", hipGetErrorString(e));
+    HostFrameJob job;
+    if ((rc = job.open("vdenoise", scene, 3 * plane, 2 * sums + ws_bytes + 3 * plane))) return rc;
+    char* acc = job.take(2 * sums);                      // the two accumulators, back to back
+    char* ws = job.take(ws_bytes);
+    rt_color* planes = (rt_color*)job.take(3 * plane);
+    const hipError_t e = hipMemsetAsync(acc, 0, 2 * sums, job.stream());
+    if (e != hipSuccess) return fail(RT_EDEVICE, "vdenoise clear: %s", hipGetErrorString(e));
     rt_params half = *params;
     half.nbRayonParPixel = S / 2;
     const rt_tiling whole = {0, H, 0, 1, 1};
     for (int k = 0; k < 2; ++k)
-        if ((rc = rt_accumulate_async(sc.get(), &half, (long long)k * (S / 2), &whole, acc[k], ps->st))) return rc;
-    const rt_frame fr = {(rt_color*)planes, albedo ? (rt_color*)(planes + plane) : nullptr,
-                         normal ? (rt_color*)(planes + 2 * plane) : nullptr, nullptr};
-    if ((rc = rt_vdenoise_async(W, H, acc[0], acc[1], S / 2, vparams, buf + 2 * sums, ws_bytes, &fr, ps->st)))
+        if ((rc = rt_accumulate_async(job.scene(), &half, (long long)k * (S / 2), &whole, (double*)(acc + k * sums),
+                                      job.stream())))
+            return rc;
+    const rt_frame fr = {planes, albedo ? planes + npx : nullptr, normal ? planes + 2 * npx : nullptr, nullptr};
+    if ((rc = rt_vdenoise_async(W, H, (double*)acc, (double*)(acc + sums), S / 2, vparams, ws, ws_bytes, &fr,
+                                job.stream())))
         return rc;
-    for (int pl = 0; pl < 3 && e == hipSuccess; ++pl)
-        if (dst[pl])
-            e = hipMemcpyAsync((char*)ps->host + pl * plane, planes + pl * plane, plane, hipMemcpyDeviceToHost, ps->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(ps->st);
-    if (e != hipSuccess) return fail(RT_EDEVICE, "vdenoise: %s", hipGetErrorString(e));
-    for (int pl = 0; pl < 3; ++pl)
-        if (dst[pl]) std::memcpy(dst[pl], (char*)ps->host + pl * plane, plane);
-    return RT_OK;
+    return job.finish({{canva, planes, plane}, {albedo, planes + npx, plane}, {normal, planes + 2 * npx, plane}});
 }
 
 }  // extern "C"

@@ -1,8 +1,11 @@
 // rt_drop_in.cpp — the C-ABI's host-buffer drop-ins (rt_render_rows /
-// rt_fill_canva) with their stream pool and scene cache, and the one device
-// slot's render (rt_host_slots.h) that they share with rt_gather.cpp.
+// rt_fill_canva) with their stream pool and scene cache, the one device
+// slot's render (rt_host_slots.h) that they share with rt_gather.cpp, and the
+// whole-frame job (HostFrameJob) of the single-device renders and filters into
+// host arrays (rt_denoise_api.cpp, rt_adaptive_api.cpp).
 #include <algorithm>
 #include <atomic>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <thread>
@@ -184,6 +187,51 @@ int RenderSlot::render(int device, const rt_scene* scene, const rt_params* param
     }
     if (go && (e = hipEventRecord(rendered, stream->st)) != hipSuccess)
         return fail(RT_EDEVICE, "device %d event: %s", device, hipGetErrorString(e));
+    return RT_OK;
+}
+
+int HostFrameJob::open(const char* name, const rt_scene* scene, size_t host_bytes, size_t device_bytes)
+{
+    what = name;
+    int rc, dev;
+    if ((rc = first_device(dev))) return rc;
+    if (scene && (rc = scene_cache_get(dev, scene, sc))) return rc;
+    if ((rc = lease.acquire(dev, true))) return rc;     // drained on every return: the caller reads its arrays next
+    current.emplace(dev);
+    hipError_t e = lease->reserve_host(host_bytes);
+    if (e == hipSuccess) e = buf.alloc(device_bytes, lease->st, dev);
+    if (e != hipSuccess) return fail(RT_ENOMEM, "%s buffers: %s", what, hipGetErrorString(e));
+    return RT_OK;
+}
+
+// (a caller whose pieces exceed what it opened the job with must not get as far as the device)
+char* HostFrameJob::bump(void* base, size_t size, size_t& used, size_t bytes)
+{
+    if (bytes > size - used) std::abort();
+    used += bytes;
+    return (char*)base + used - bytes;
+}
+
+int HostFrameJob::upload(void* dst_dev, const void* src_host, size_t bytes)
+{
+    char* host = stage(bytes);
+    std::memcpy(host, src_host, bytes);
+    const hipError_t e = hipMemcpyAsync(dst_dev, host, bytes, hipMemcpyHostToDevice, lease->st);
+    if (e != hipSuccess) return fail(RT_EDEVICE, "%s upload: %s", what, hipGetErrorString(e));
+    return RT_OK;
+}
+
+int HostFrameJob::finish(std::initializer_list<Copy> copies)
+{
+    hipError_t e = hipSuccess;
+    staged = 0;              // behind the uploads in stream order, so their staging is free again
+    for (const Copy& c : copies)
+        if (c.host && e == hipSuccess) e = hipMemcpyAsync(stage(c.bytes), c.dev, c.bytes, hipMemcpyDeviceToHost, lease->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(lease->st);
+    if (e != hipSuccess) return fail(RT_EDEVICE, "%s: %s", what, hipGetErrorString(e));
+    staged = 0;
+    for (const Copy& c : copies)
+        if (c.host) std::memcpy(c.host, stage(c.bytes), c.bytes);
     return RT_OK;
 }
 

@@ -1,9 +1,13 @@
 // rt_host_slots.h — what a host-buffer drop-in or a gather holds while it
 // runs, as owning types: an event, a stream-ordered device buffer, a pooled
-// stream, and one device slot's render.  Shared by rt_drop_in.cpp (the pool,
-// the scene cache, RenderSlot::render), rt_gather.cpp and rt_denoise_api.cpp.
+// stream, one device slot's render, and one whole frame's way to the host
+// (HostFrameJob).  Shared by rt_drop_in.cpp (the pool, the scene cache,
+// RenderSlot::render, HostFrameJob), rt_gather.cpp, rt_denoise_api.cpp and
+// rt_adaptive_api.cpp.
 #pragma once
+#include <initializer_list>
 #include <memory>
+#include <optional>
 
 #include "rt_api_internal.h"
 
@@ -31,12 +35,6 @@ struct PooledStream {
 
 // The device copy of *sc on `device` from the scene cache, uploaded on first use.
 int scene_cache_get(int device, const rt_scene* sc, std::shared_ptr<rt_device_scene>& out);
-
-struct NoCopy {
-    NoCopy() = default;
-    NoCopy(const NoCopy&) = delete;
-    NoCopy& operator=(const NoCopy&) = delete;
-};
 
 // An event without timing, destroyed with its owner.
 struct Event : NoCopy {
@@ -101,6 +99,40 @@ struct RenderSlot {
     // stream right behind the render, before `rendered`.
     int render(int device, const rt_scene* scene, const rt_params* params, const rt_tiling& t, int row_end,
                rt_color* const* want, hipEvent_t go, bool pack_canva = false);
+};
+
+// One whole frame rendered or filtered into the caller's host arrays on the
+// first device of rt_init's list (rt_render_vdenoised, rt_render_adaptive[_vdenoised],
+// rt_denoise_host): open, enqueue the async entry points on stream() with
+// pieces of the device buffer, finish.  Members are destroyed last to first,
+// and the job relies on that order: the buffer's stream-ordered free is
+// enqueued first, then the caller's device is current again, then the lease
+// waits for the stream (the caller reads its arrays next) and returns it.
+struct HostFrameJob {
+    struct Copy { void* host; const void* dev; size_t bytes; };     // host: the caller's array; null: not asked for
+    // `scene` may be null.  host_bytes: the pinned staging, enough for all that upload is given and for all that
+    // finish copies.  A failed reservation or allocation is RT_ENOMEM "<what> buffers: ...".
+    int open(const char* what, const rt_scene* scene, size_t host_bytes, size_t device_bytes);
+    hipStream_t stream() const { return lease->st; }
+    const rt_device_scene* scene() const { return sc.get(); }
+    // The next `bytes` of the device buffer, back to back (callers round up to 16 where a piece needs it).  More
+    // than open was given is a bug of the entry point, never user input: an invariant check that abort()s.
+    char* take(size_t bytes) { return bump(buf.p, buf.bytes, taken, bytes); }
+    // H2D through the staging, behind what the stream already holds (RT_EDEVICE "<what> upload: ...")
+    int upload(void* dst_dev, const void* src_host, size_t bytes);
+    // D2H of every asked-for copy into the staging, the stream drained, then the staging into the caller's
+    // arrays: none of them is written unless everything succeeded (RT_EDEVICE "<what>: ...")
+    int finish(std::initializer_list<Copy> copies);
+
+private:
+    const char* what = "";
+    std::shared_ptr<rt_device_scene> sc;
+    StreamLease lease;
+    std::optional<DeviceGuard> current;      // the job's device, from open on
+    StreamBuffer buf;
+    size_t taken = 0, staged = 0;
+    static char* bump(void* base, size_t size, size_t& used, size_t bytes);
+    char* stage(size_t bytes) { return bump(lease->host, lease->host_bytes, staged, bytes); }   // of the pinned staging
 };
 
 }  // namespace rt

@@ -231,6 +231,19 @@ int launch_render_list(const KParams& kp, const RenderPlan& plan, const ListArgs
 // kListTaskWords launch-private words kListTaskOffset words behind it (the band's task count, entry count and
 // division magic, which a prologue kernel derives from the device's count word).
 constexpr int kListTaskOffset = 16, kListTaskWords = 3;
+// A launch's stream-ordered scratch (LaunchScratch, rt_api_internal.h), one layout for every launch: the uniform
+// block; in double kTaskCtrDouble the queue's task counter, on a 64-byte line of its own; the list form's words
+// kListTaskOffset words behind it, on the next line.  The kernels read through these offsets.
+constexpr int kTaskCtrDouble = ((U_COUNT + 7) / 8 + 1) * 8;
+constexpr size_t kTaskCtrByte = kTaskCtrDouble * sizeof(double);
+constexpr size_t kLaunchScratchBytes = kTaskCtrByte + (kListTaskOffset + kListTaskWords) * sizeof(unsigned);
+static_assert(kTaskCtrByte % 64 == 0 && kTaskCtrByte >= U_COUNT * sizeof(double),
+              "the counter starts a 64-byte line past the uniforms");
+static_assert(kListTaskOffset * sizeof(unsigned) == 64, "the list words start on the line behind the counter's");
+constexpr int kListLastWord = kListTaskOffset + kListTaskWords - 1;    // counted from the counter, as the kernels index
+static_assert(kTaskCtrByte + (kListLastWord + 1) * sizeof(unsigned) <= kLaunchScratchBytes,
+              "the allocation covers the last list word");
+static_assert(U_COUNT != 20 || (kTaskCtrByte == 256 && kLaunchScratchBytes == 332), "the offsets of 20 uniforms");
 int launch_render_list_queue(const KParams& kp, const RenderPlan& plan, const ListArgs& la, void* stream);
 // combine_list_kernel (rt_adaptive.hip) for one band, as launch_render_list ends with it.
 int launch_combine_list(const KParams& kp, const ListArgs& la, void* stream);

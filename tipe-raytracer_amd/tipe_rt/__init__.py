@@ -28,6 +28,84 @@ class RTError(RuntimeError):
 _lib = None
 _host = None
 
+# rt_denoise_fn (rt.h): denoiser()'s signature, denoiser.h:31
+DENOISE_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p, Camera, C.c_void_p, C.c_void_p)
+_hook_ref = None
+
+_P = C.POINTER
+_int, _ll, _ull, _ptr, _size, _str = C.c_int, C.c_longlong, C.c_ulonglong, C.c_void_p, C.c_size_t, C.c_char_p
+_SC, _PA, _TI, _FR, _DP, _VP, _AP = (_P(t) for t in (Scene, Params, Tiling, Frame, DenoiseParams, VDenoiseParams,
+                                                     AdaptiveParams))
+_ASSEMBLE = [_ptr, _ll, _int, _int, _int, _int, _int, _ptr, _ptr]
+
+# Every function include/rt/rt.h declares: name -> (restype, argtypes), in the
+# header's order.  Device and host arrays and streams go over as void pointers.
+# tests/test_abi.py holds the names and the argument counts against the header.
+PROTOTYPES = {
+    "rt_params_init": (None, [_PA]),
+    "rt_init": (_int, [_int, _P(_int)]),
+    "rt_shutdown": (None, []),
+    "rt_last_error": (_str, []),
+    "rt_abi_version": (_int, []),
+    "rt_last_render_kernel": (_str, []),
+    "rt_last_list_kernel": (_str, []),
+    "rt_version": (_str, []),
+    "rt_device_count": (_int, []),
+    "rt_render_rows": (_int, [_SC, _PA, _int, _int, _ptr, _ptr, _ptr]),
+    "rt_fill_canva": (_ptr, [_ptr]),
+    "rt_set_fill_spp_chunks": (_int, [_int]),
+    "rt_set_fill_precision": (_int, [_int]),
+    "rt_scene_cache_clear": (_int, []),
+    "rt_scene_upload": (_int, [_int, _SC, _P(_ptr)]),
+    "rt_scene_release": (None, [_ptr]),
+    "rt_render_async": (_int, [_ptr, _PA, _TI, _FR, _ptr]),
+    "rt_assemble_async": (_int, _ASSEMBLE),
+    "rt_gather_async": (_int, [_int, _P(_int), _P(_ptr), _int, _int, _int, _int, _int, _ptr, _ptr]),
+    "rt_render_gather_async": (_int, [_SC, _PA, _int, _FR, _ptr]),
+    "rt_last_gather_transport": (_str, []),
+    "rt_peer_access": (_int, [_int, _int]),
+    "rt_canva_pack_async": (_int, [_ll, _ptr, _ptr, _ptr]),
+    "rt_canva_unpack_async": (_int, [_ll, _ptr, _ptr, _ptr]),
+    "rt_canva_unpack_host": (_int, [_ll, _ptr, _ptr]),
+    "rt_assemble_packed_async": (_int, _ASSEMBLE),
+    "rt_set_fill_packed_canva": (_int, [_int]),
+    "rt_count_async": (_int, [_ptr, _PA, _TI, _ptr, _ptr]),
+    "rt_accumulate_async": (_int, [_ptr, _PA, _ll, _TI, _ptr, _ptr]),
+    "rt_resolve_async": (_int, [_ptr, _PA, _int, _TI, _FR, _ptr]),
+    "rt_set_zero_throughput_exit": (_int, [_int]),
+    "rt_set_accumulate_queue": (_int, [_int]),
+    "rt_set_denoise_hook": (None, [DENOISE_FN]),
+    "rt_get_denoise_hook": (_ptr, []),
+    "rt_denoise_pack": (_int, [_int, _int] + [_ptr] * 6),
+    "rt_denoise_unpack": (_int, [_int, _int, _ptr, _ptr]),
+    "rt_denoise_pack_async": (_int, [_int, _int, _FR] + [_ptr] * 4),
+    "rt_denoise_params_init": (None, [_DP]),
+    "rt_denoise_workspace_bytes": (_size, [_int, _int]),
+    "rt_denoise_async": (_int, [_int, _int, _FR, _DP, _ptr, _size, _ptr, _ptr]),
+    "rt_denoise_host": (_int, [_int, _int, _ptr, _ptr, _ptr, _DP]),
+    "rt_denoise_atrous": (None, [_int, _int, _ptr, Camera, _ptr, _ptr]),
+    "rt_set_denoise_params": (_int, [_DP]),
+    "rt_vdenoise_params_init": (None, [_VP]),
+    "rt_vdenoise_workspace_bytes": (_size, [_int, _int]),
+    "rt_vdenoise_async": (_int, [_int, _int, _ptr, _ptr, _int, _VP, _ptr, _size, _FR, _ptr]),
+    "rt_render_vdenoised": (_int, [_SC, _PA, _VP, _ptr, _ptr, _ptr]),
+    "rt_accumulate_list_async": (_int, [_ptr, _PA, _ll, _ptr, _ptr, C.c_uint, _ptr, _ptr]),
+    "rt_adaptive_select_async": (_int, [_int, _int, _ptr, _ptr, _int, C.c_float, _int, _ptr, _ptr, _ptr, _ptr, _size, _ptr]),
+    "rt_adaptive_workspace_bytes": (_size, [_int, _int]),
+    "rt_adaptive_params_init": (None, [_AP]),
+    "rt_adaptive_async": (_int, [_ptr, _PA, _AP, _ptr, _ptr, _ptr, _ptr, _size, _FR, _ptr]),
+    "rt_resolve_adaptive_async": (_int, [_int, _int, _ptr, _ptr, _ptr, _int, _FR, _ptr]),
+    "rt_render_adaptive": (_int, [_SC, _PA, _AP, _ptr, _ptr, _ptr, _ptr]),
+    "rt_vdenoise_adaptive_async": (_int, [_int, _int, _ptr, _ptr, _ptr, _int, _VP, _ptr, _size, _FR, _ptr]),
+    "rt_render_adaptive_vdenoised": (_int, [_SC, _PA, _AP, _VP, _ptr, _ptr, _ptr, _ptr]),
+    "rt_selftest_math": (_int, [_int, _ptr, _ptr, _int]),
+    "rt_verify_sampler_phi": (_int, [_ull, _ull, _ptr]),
+    "rt_verify_sphere_pass": (_int, [_SC, _ptr, _ll, _ptr]),
+    "rt_verify_normalize": (_int, [_ull, _ull, _ptr]),
+    "rt_verify_texel_map": (_int, [_SC, _ptr, _ptr, _ll, _ptr]),
+}
+EXPORTED_SYMBOLS = list(PROTOTYPES)
+
 
 def lib():
     """librt_hip.so with prototypes.  Raises if it was not built."""
@@ -44,123 +122,29 @@ def lib():
             raise RuntimeError("librt_hip.so not built (%s): run `make -C tipe-raytracer_amd` "
                                "or __graft_entry__.build(); there is no CPU fallback" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        P = C.POINTER
-        L.rt_params_init.argtypes = [P(Params)]
-        L.rt_init.argtypes = [C.c_int, P(C.c_int)]
-        L.rt_last_error.restype = C.c_char_p
-        L.rt_version.restype = C.c_char_p
-        L.rt_last_render_kernel.restype = C.c_char_p
-        L.rt_last_gather_transport.restype = C.c_char_p
-        L.rt_abi_version.restype = C.c_int
-        L.rt_render_rows.argtypes = [P(Scene), P(Params), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rt_fill_canva.argtypes = [C.c_void_p]
-        L.rt_fill_canva.restype = C.c_void_p
-        L.rt_scene_upload.argtypes = [C.c_int, P(Scene), P(C.c_void_p)]
-        L.rt_scene_release.argtypes = [C.c_void_p]
-        L.rt_render_async.argtypes = [C.c_void_p, P(Params), P(Tiling), P(Frame), C.c_void_p]
-        L.rt_count_async.argtypes = [C.c_void_p, P(Params), P(Tiling), C.c_void_p, C.c_void_p]
-        L.rt_assemble_async.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_void_p, C.c_void_p]
-        L.rt_gather_async.argtypes = [C.c_int, P(C.c_int), P(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
-                                      C.c_int, C.c_void_p, C.c_void_p]
-        L.rt_render_gather_async.argtypes = [P(Scene), P(Params), C.c_int, P(Frame), C.c_void_p]
-        L.rt_peer_access.argtypes = [C.c_int, C.c_int]
-        L.rt_selftest_math.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-        L.rt_verify_sampler_phi.argtypes = [C.c_ulonglong, C.c_ulonglong, C.c_void_p]
-        L.rt_verify_sphere_pass.argtypes = [P(Scene), C.c_void_p, C.c_longlong, C.c_void_p]
-        if hasattr(L, "rt_verify_normalize"):    # (older builds in A/B runs lack the diagnostic)
-            L.rt_verify_normalize.argtypes = [C.c_ulonglong, C.c_ulonglong, C.c_void_p]
-        if hasattr(L, "rt_verify_texel_map"):
-            L.rt_verify_texel_map.argtypes = [P(Scene), C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
-        L.rt_accumulate_async.argtypes = [C.c_void_p, P(Params), C.c_longlong, P(Tiling), C.c_void_p, C.c_void_p]
-        L.rt_resolve_async.argtypes = [C.c_void_p, P(Params), C.c_int, P(Tiling), P(Frame), C.c_void_p]
-        L.rt_set_denoise_hook.argtypes = [DENOISE_FN]
-        L.rt_get_denoise_hook.restype = C.c_void_p
-        L.rt_set_zero_throughput_exit.argtypes = [C.c_int]
-        L.rt_set_zero_throughput_exit.restype = C.c_int
-        L.rt_set_fill_spp_chunks.argtypes = [C.c_int]
-        L.rt_set_fill_spp_chunks.restype = C.c_int
-        L.rt_set_fill_precision.argtypes = [C.c_int]
-        L.rt_set_fill_precision.restype = C.c_int
-        L.rt_scene_cache_clear.restype = C.c_int
-        L.rt_denoise_pack.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6
-        L.rt_denoise_unpack.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.rt_denoise_pack_async.argtypes = [C.c_int, C.c_int, P(Frame)] + [C.c_void_p] * 4
-        L.rt_denoise_params_init.argtypes = [P(DenoiseParams)]
-        L.rt_denoise_params_init.restype = None
-        L.rt_denoise_workspace_bytes.argtypes = [C.c_int, C.c_int]
-        L.rt_denoise_workspace_bytes.restype = C.c_size_t
-        L.rt_denoise_async.argtypes = [C.c_int, C.c_int, P(Frame), P(DenoiseParams), C.c_void_p, C.c_size_t,
-                                       C.c_void_p, C.c_void_p]
-        L.rt_denoise_host.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, P(DenoiseParams)]
-        L.rt_denoise_atrous.argtypes = [C.c_int, C.c_int, C.c_void_p, Camera, C.c_void_p, C.c_void_p]
-        L.rt_denoise_atrous.restype = None
-        L.rt_set_denoise_params.argtypes = [P(DenoiseParams)]
-        if hasattr(L, "rt_vdenoise_async"):      # (added to ABI 5: older builds in A/B runs lack it)
-            L.rt_vdenoise_params_init.argtypes = [P(VDenoiseParams)]
-            L.rt_vdenoise_params_init.restype = None
-            L.rt_vdenoise_workspace_bytes.argtypes = [C.c_int, C.c_int]
-            L.rt_vdenoise_workspace_bytes.restype = C.c_size_t
-            L.rt_vdenoise_async.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, P(VDenoiseParams),
-                                            C.c_void_p, C.c_size_t, P(Frame), C.c_void_p]
-            L.rt_render_vdenoised.argtypes = [P(Scene), P(Params), P(VDenoiseParams), C.c_void_p, C.c_void_p,
-                                              C.c_void_p]
-        if hasattr(L, "rt_adaptive_async"):      # (added to ABI 5 as well)
-            L.rt_accumulate_list_async.argtypes = [C.c_void_p, P(Params), C.c_longlong, C.c_void_p, C.c_void_p,
-                                                   C.c_uint, C.c_void_p, C.c_void_p]
-            L.rt_adaptive_workspace_bytes.argtypes = [C.c_int, C.c_int]
-            L.rt_adaptive_workspace_bytes.restype = C.c_size_t
-            L.rt_adaptive_select_async.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
-                                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                   C.c_size_t, C.c_void_p]
-            L.rt_adaptive_params_init.argtypes = [P(AdaptiveParams)]
-            L.rt_adaptive_params_init.restype = None
-            L.rt_adaptive_async.argtypes = [C.c_void_p, P(Params), P(AdaptiveParams), C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_size_t, P(Frame), C.c_void_p]
-            L.rt_resolve_adaptive_async.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                                    P(Frame), C.c_void_p]
-            L.rt_render_adaptive.argtypes = [P(Scene), P(Params), P(AdaptiveParams), C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p]
-        if hasattr(L, "rt_vdenoise_adaptive_async"):     # (added to ABI 5 as well)
-            L.rt_vdenoise_adaptive_async.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                                     P(VDenoiseParams), C.c_void_p, C.c_size_t, P(Frame), C.c_void_p]
-            L.rt_render_adaptive_vdenoised.argtypes = [P(Scene), P(Params), P(AdaptiveParams), P(VDenoiseParams),
-                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(L, "rt_set_accumulate_queue"):        # (added to ABI 5 as well)
-            L.rt_set_accumulate_queue.argtypes = [C.c_int]
-            L.rt_set_accumulate_queue.restype = C.c_int
-            L.rt_last_list_kernel.restype = C.c_char_p
-        if hasattr(L, "rt_canva_pack_async"):            # (added to ABI 5 as well)
-            L.rt_canva_pack_async.argtypes = [C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.rt_canva_unpack_async.argtypes = [C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.rt_canva_unpack_host.argtypes = [C.c_longlong, C.c_void_p, C.c_void_p]
-            L.rt_assemble_packed_async.argtypes = L.rt_assemble_async.argtypes
-            L.rt_set_fill_packed_canva.argtypes = [C.c_int]
-            L.rt_set_fill_packed_canva.restype = C.c_int
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(L, name, None)      # an older build in an A/B run (RT_HIP_LIB) may lack the newer ones
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
 
-EXPORTED_SYMBOLS = ["rt_params_init", "rt_init", "rt_shutdown", "rt_last_error", "rt_version",
-                    "rt_device_count", "rt_render_rows", "rt_fill_canva", "rt_scene_upload",
-                    "rt_scene_release", "rt_render_async", "rt_assemble_async", "rt_count_async",
-                    "rt_selftest_math", "rt_accumulate_async", "rt_resolve_async", "rt_set_denoise_hook", "rt_get_denoise_hook", "rt_denoise_pack",
-                    "rt_denoise_unpack", "rt_denoise_pack_async", "rt_verify_sampler_phi",
-                    "rt_verify_sphere_pass", "rt_verify_normalize", "rt_verify_texel_map", "rt_set_zero_throughput_exit", "rt_set_fill_spp_chunks", "rt_set_fill_precision",
-                    "rt_scene_cache_clear", "rt_gather_async", "rt_render_gather_async", "rt_peer_access",
-                    "rt_last_render_kernel", "rt_denoise_params_init", "rt_denoise_workspace_bytes",
-                    "rt_denoise_async", "rt_denoise_host", "rt_denoise_atrous", "rt_set_denoise_params",
-                    "rt_vdenoise_params_init", "rt_vdenoise_workspace_bytes", "rt_vdenoise_async",
-                    "rt_render_vdenoised", "rt_accumulate_list_async", "rt_adaptive_select_async",
-                    "rt_adaptive_workspace_bytes", "rt_adaptive_params_init", "rt_adaptive_async",
-                    "rt_resolve_adaptive_async", "rt_render_adaptive", "rt_vdenoise_adaptive_async",
-                    "rt_render_adaptive_vdenoised", "rt_set_accumulate_queue", "rt_last_list_kernel",
-                    "rt_canva_pack_async", "rt_canva_unpack_async", "rt_canva_unpack_host",
-                    "rt_assemble_packed_async", "rt_set_fill_packed_canva"]
+def _planes(params, albedo, normal):
+    """Fresh (H, W, 3) float64 canva / albedo / normal (None where not asked
+    for) and the pointers to pass: the data pointer, or None."""
+    W, H = params.largeur_image, params.hauteur_image
+    arrays = [np.zeros((H, W, 3)) if want else None for want in (True, albedo, normal)]
+    return arrays, [None if a is None else a.ctypes.data for a in arrays]
 
-# rt_denoise_fn (rt.h): denoiser()'s signature, denoiser.h:31
-DENOISE_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p, Camera, C.c_void_p, C.c_void_p)
-_hook_ref = None
+
+def _with_overrides(p, init, values):
+    """p after the library's init(p), with its fields, in their order, replaced by the values that are not None."""
+    init(C.byref(p))
+    for (name, _), v in zip(p._fields_, values):
+        if v is not None:
+            setattr(p, name, v)
+    return p
 
 
 def set_zero_throughput_exit(enable):
@@ -257,13 +241,8 @@ def denoise_unpack(color3):
 
 def denoise_params(iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None):
     """rt_denoise_params_init's defaults (4 passes; sigmas 1, 0.5, 0.25) with the given fields replaced."""
-    p = DenoiseParams()
-    lib().rt_denoise_params_init(C.byref(p))
-    for name, v in (("iterations", iterations), ("sigma_color", sigma_color), ("sigma_normal", sigma_normal),
-                    ("sigma_albedo", sigma_albedo)):
-        if v is not None:
-            setattr(p, name, v)
-    return p
+    return _with_overrides(DenoiseParams(), lib().rt_denoise_params_init,
+                           (iterations, sigma_color, sigma_normal, sigma_albedo))
 
 
 def denoise(canva, albedo=None, normal=None, params=None):
@@ -297,13 +276,8 @@ def set_denoise_atrous(enable=True, params=None):
 
 def vdenoise_params(iterations=None, sigma_luminance=None, sigma_normal=None, sigma_albedo=None):
     """rt_vdenoise_params_init's defaults (4 passes; sigmas 4, 0.5, 0.25) with the given fields replaced."""
-    p = VDenoiseParams()
-    lib().rt_vdenoise_params_init(C.byref(p))
-    for name, v in (("iterations", iterations), ("sigma_luminance", sigma_luminance), ("sigma_normal", sigma_normal),
-                    ("sigma_albedo", sigma_albedo)):
-        if v is not None:
-            setattr(p, name, v)
-    return p
+    return _with_overrides(VDenoiseParams(), lib().rt_vdenoise_params_init,
+                           (iterations, sigma_luminance, sigma_normal, sigma_albedo))
 
 
 def vdenoise_async(W, H, sums_a_ptr, sums_b_ptr, spp_half, params, workspace_ptr, workspace_bytes, canva_ptr,
@@ -318,25 +292,15 @@ def vdenoise_async(W, H, sums_a_ptr, sums_b_ptr, spp_half, params, workspace_ptr
 def render_vdenoised(scene, params, vparams=None, albedo=True, normal=True):
     """rt_render_vdenoised into fresh (H, W, 3) float64 arrays (canva, albedo,
     normal): the frame's two sample halves rendered and filtered on the device."""
-    W, H = params.largeur_image, params.hauteur_image
-    canva = np.zeros((H, W, 3))
-    alb = np.zeros((H, W, 3)) if albedo else None
-    nrm = np.zeros((H, W, 3)) if normal else None
+    planes, ptrs = _planes(params, albedo, normal)
     vp = vparams if vparams is not None else vdenoise_params()
-    check(lib().rt_render_vdenoised(C.byref(scene), C.byref(params), C.byref(vp), canva.ctypes.data,
-                                    alb.ctypes.data if alb is not None else None,
-                                    nrm.ctypes.data if nrm is not None else None))
-    return canva, alb, nrm
+    check(lib().rt_render_vdenoised(C.byref(scene), C.byref(params), C.byref(vp), *ptrs))
+    return tuple(planes)
 
 
 def adaptive_params(first_half=None, max_rounds=None, tolerance=None):
     """rt_adaptive_params_init's defaults (8, 5, 1/64) with the given fields replaced."""
-    p = AdaptiveParams()
-    lib().rt_adaptive_params_init(C.byref(p))
-    for name, v in (("first_half", first_half), ("max_rounds", max_rounds), ("tolerance", tolerance)):
-        if v is not None:
-            setattr(p, name, v)
-    return p
+    return _with_overrides(AdaptiveParams(), lib().rt_adaptive_params_init, (first_half, max_rounds, tolerance))
 
 
 def accumulate_list_async(dscene, params, sample_offset, list_ptr, count_ptr, list_cap, sums_ptr, stream=None):
@@ -371,16 +335,11 @@ def resolve_adaptive_async(W, H, sums_a_ptr, sums_b_ptr, rounds_ptr, first_half,
 def render_adaptive(scene, params, aparams=None, albedo=True, normal=True):
     """rt_render_adaptive into fresh arrays: (canva, albedo, normal, rounds),
     three (H, W, 3) float64 planes and the (H, W) int32 round counts."""
-    W, H = params.largeur_image, params.hauteur_image
-    canva = np.zeros((H, W, 3))
-    alb = np.zeros((H, W, 3)) if albedo else None
-    nrm = np.zeros((H, W, 3)) if normal else None
-    rounds = np.zeros((H, W), dtype=np.int32)
+    planes, ptrs = _planes(params, albedo, normal)
+    rounds = np.zeros(planes[0].shape[:2], dtype=np.int32)
     ap = aparams if aparams is not None else adaptive_params()
-    check(lib().rt_render_adaptive(C.byref(scene), C.byref(params), C.byref(ap), canva.ctypes.data,
-                                   alb.ctypes.data if alb is not None else None,
-                                   nrm.ctypes.data if nrm is not None else None, rounds.ctypes.data))
-    return canva, alb, nrm, rounds
+    check(lib().rt_render_adaptive(C.byref(scene), C.byref(params), C.byref(ap), *ptrs, rounds.ctypes.data))
+    return (*planes, rounds)
 
 
 def vdenoise_adaptive_async(W, H, sums_a_ptr, sums_b_ptr, rounds_ptr, first_half, params, workspace_ptr,
@@ -396,17 +355,13 @@ def vdenoise_adaptive_async(W, H, sums_a_ptr, sums_b_ptr, rounds_ptr, first_half
 def render_adaptive_vdenoised(scene, params, aparams=None, vparams=None, albedo=True, normal=True):
     """rt_render_adaptive_vdenoised into fresh arrays: (canva, albedo, normal,
     rounds) as render_adaptive's, the planes filtered by the variance-guided denoiser."""
-    W, H = params.largeur_image, params.hauteur_image
-    canva = np.zeros((H, W, 3))
-    alb = np.zeros((H, W, 3)) if albedo else None
-    nrm = np.zeros((H, W, 3)) if normal else None
-    rounds = np.zeros((H, W), dtype=np.int32)
+    planes, ptrs = _planes(params, albedo, normal)
+    rounds = np.zeros(planes[0].shape[:2], dtype=np.int32)
     ap = aparams if aparams is not None else adaptive_params()
     vp = vparams if vparams is not None else vdenoise_params()
-    check(lib().rt_render_adaptive_vdenoised(C.byref(scene), C.byref(params), C.byref(ap), C.byref(vp),
-                                             canva.ctypes.data, alb.ctypes.data if alb is not None else None,
-                                             nrm.ctypes.data if nrm is not None else None, rounds.ctypes.data))
-    return canva, alb, nrm, rounds
+    check(lib().rt_render_adaptive_vdenoised(C.byref(scene), C.byref(params), C.byref(ap), C.byref(vp), *ptrs,
+                                             rounds.ctypes.data))
+    return (*planes, rounds)
 
 
 def last_gather_transport():
@@ -490,16 +445,11 @@ def make_params(W, H, spp, bounces, cam, focus=3.0, aperture=(0.0, 0.0), use_ao=
 
 def render_rows(scene, params, row_hi=None, row_lo=0, albedo=True, normal=True):
     """rt_render_rows into fresh (H, W, 3) float64 arrays (canva, albedo, normal)."""
-    W, H = params.largeur_image, params.hauteur_image
     if row_hi is None:
-        row_hi = H - 1
-    canva = np.zeros((H, W, 3))
-    alb = np.zeros((H, W, 3)) if albedo else None
-    nrm = np.zeros((H, W, 3)) if normal else None
-    check(lib().rt_render_rows(C.byref(scene), C.byref(params), row_hi, row_lo, canva.ctypes.data,
-                               alb.ctypes.data if alb is not None else None,
-                               nrm.ctypes.data if nrm is not None else None))
-    return canva, alb, nrm
+        row_hi = params.hauteur_image - 1
+    planes, ptrs = _planes(params, albedo, normal)
+    check(lib().rt_render_rows(C.byref(scene), C.byref(params), row_hi, row_lo, *ptrs))
+    return tuple(planes)
 
 
 class DeviceScene:
